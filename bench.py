@@ -2,7 +2,13 @@
 """Benchmark of the hot path: SPLinearWithLoRA.forward on GPT-2-small c_fc (768 -> 3072), 4-bit minmax
 per-channel, LoRA rank 64, batch 8 x seq 1024 tokens per GPU (BASELINE.json metric; SURVEY.md §8d headline).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, dtype, the calibration
+it did).  --full adds every secondary figure and check to the line: the event-timed dominant kernel and its roofline, repeats
+of the K-step region, the cached-operand and cold-cache figures, the vendor-GEMM yardstick, and the CPU oracle's baseline
+and parity gate on the timed output.  --dump-outputs DIR writes the last timed step's output (a fixed, seeded sample of its
+token rows) as DIR/y.npy, so that two builds can be compared output for output.
 
 N > 1 either way: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (the ranks read
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), or started bare -- then this process, BEFORE it touches the
@@ -41,7 +47,8 @@ PEAK = {"f32": 157.3, "f16": 2500.0, "i8": 5000.0, "hbm_gbs": 8000.0}   # MI355X
 SETUP_STEPS = 2000        # untimed, before the W warm-ups: grows the workspaces and lets the clocks settle (~0.2 s; not part of W or K).
                           # Measured (tools/setup_steps_ab.sh, one box, --steps 20 --warmup 5): 200 -> 0.0994 / 0.1016 / 0.1013 ms per step in the
                           # first timed region, 2000 -> 0.0963 / 0.0965: after 20 ms of work the chip has not reached the clock it then holds.
-STAT_REPEATS = 5          # extra repetitions of the K-step region for the median / min figure
+STAT_REPEATS = 5          # extra repetitions of the K-step region for the median / min figure (--full)
+DUMP_ROWS = 4096          # --dump-outputs: token rows of y written (seeded sample of M_TOKENS), 4096 x 3072 fp32 = 48 MiB
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -208,7 +215,13 @@ def main():
     ap.add_argument("--path", choices=["auto", "f32", "f16x2", "f16x3", "i8"], default="auto")
     ap.add_argument("--hoist-weights", action="store_true",
                     help="reuse prepared weight operands across steps (eval-mode behaviour of the module)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: kernel events + roofline, repeats of the "
+                         "timed region, cached-operand and cold-cache figures, vendor-GEMM yardstick, CPU baseline + parity")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline and parity gate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help=f"write the last timed step's output y (rank 0; {DUMP_ROWS} token rows picked by a fixed seed) as "
+                         "DIR/y.npy, float32")
     ap.add_argument("--setup-steps", type=int, default=SETUP_STEPS,
                     help="untimed forwards BEFORE the --warmup steps (workspace growth, code-object load, clock ramp); 0 = the "
                          "timed region starts after exactly --warmup warm-ups")
@@ -219,6 +232,8 @@ def main():
                     help="no GPU: rehearse launcher, rank formation (gloo), the one calibration all-reduce and the timing "
                          "protocol; prints the line with dry_run=true and no throughput")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))            # no GPU call has happened in this process
@@ -295,17 +310,19 @@ def main():
     with torch.no_grad():
         for _ in range(max(0, args.setup_steps)):          # setup, not warm-up: workspace growth, code-object load, clock ramp
             y = layer(x)
-        # the dominant kernel is timed live inside the timed region, on every EVERY-th step (an event pair costs two marker
-        # packets on the launch stream; on every step that alone took 8 % off the throughput it was meant to explain); EVERY
-        # is chosen so that even a 20-step run averages over >= 8 launches
-        EVERY = int(os.environ.get('SPQ_BENCH_EVENT_EVERY', '8'))
-        if args.steps < 64 and 'SPQ_BENCH_EVENT_EVERY' not in os.environ:
-            # a short region (the driver's 20 steps): ONE event pair inside it -- each pair is two marker packets on the launch
-            # stream, ~20 us of a 2 ms region apiece -- and the other >= 7 samples on the first repeat region below
-            EVERY = max(EVERY, args.steps)
-        n_main = (args.steps + EVERY - 1) // EVERY
-        n_extra = max(0, 8 - n_main)      # a short run: further samples ride on the first repeat region below, >= 8 launches in all
-        ev = HipEvents(n_main + n_extra)
+        ev, EVERY, n_main, n_extra = None, 1, 0, 0
+        if args.full:
+            # the dominant kernel is timed live inside the timed region, on every EVERY-th step (an event pair costs two marker
+            # packets on the launch stream; on every step that alone took 8 % off the throughput it was meant to explain); EVERY
+            # is chosen so that even a 20-step run averages over >= 8 launches
+            EVERY = int(os.environ.get('SPQ_BENCH_EVENT_EVERY', '8'))
+            if args.steps < 64 and 'SPQ_BENCH_EVENT_EVERY' not in os.environ:
+                # a short region (the driver's 20 steps): ONE event pair inside it -- each pair is two marker packets on the launch
+                # stream, ~20 us of a 2 ms region apiece -- and the other >= 7 samples on the first repeat region below
+                EVERY = max(EVERY, args.steps)
+            n_main = (args.steps + EVERY - 1) // EVERY
+            n_extra = max(0, 8 - n_main)      # a short run: further samples ride on the first repeat region below, >= 8 launches in all
+            ev = HipEvents(n_main + n_extra)
         import gc
         gc.collect(); gc.disable()        # a collector pause of the host inside a 2-ms region is a 10-20 % outlier (seen: 0.119 against 0.097 ms/step)
         # All host-side preparation (events, the collector) happens BEFORE the W warm-up steps, so that the timed region follows GPU work,
@@ -321,7 +338,7 @@ def main():
         for i in range(args.steps):
             # (a sample sits on the LAST step of its group of EVERY: in a 20-step region the one pair then lands at the region's end, where its two
             # marker packets delay nothing behind them -- at step 0 they sat in the launch ramp of the whole region)
-            layer._gemm_events = ev.pairs[i // EVERY] if (i % EVERY == EVERY - 1 or i == args.steps - 1) and i // EVERY < n_main else None
+            layer._gemm_events = ev.pairs[i // EVERY] if ev and (i % EVERY == EVERY - 1 or i == args.steps - 1) and i // EVERY < n_main else None
             y = layer(x)
         torch.cuda.synchronize()
         if world > 1:
@@ -330,9 +347,10 @@ def main():
         elapsed = time.perf_counter() - t0
         gc.enable()
         layer._gemm_events = None
+        y_last = y                         # what the timed path returned on its last step (each forward allocates a new y)
         # median / min over repeats of the same K-step region (no event markers), SURVEY.md §8d
         repeats = []
-        for rep in range(STAT_REPEATS):
+        for rep in range(STAT_REPEATS if args.full else 0):
             if rep == 0 and n_extra:       # same K-step protocol, event pairs on its first launches
                 torch.cuda.synchronize()
                 if world > 1:
@@ -354,7 +372,7 @@ def main():
     # secondary figure (not `value`): the module's eval-mode behaviour, weight-side operands reused while W/A/B and the
     # scales are unchanged; same protocol, same K
     elapsed_cached = None
-    if not args.hoist_weights:
+    if args.full and not args.hoist_weights:
         layer.cache_operands = True
         with torch.no_grad():
             for _ in range(max(3, args.warmup // 4)):
@@ -364,7 +382,7 @@ def main():
         layer.cache_operands = False
     # secondary figure: L2 / Infinity-Cache cold (a 512 MB write between forwards evicts activations, weights and operands)
     cold_ms = None
-    if world == 1:
+    if args.full and world == 1:
         flush = torch.empty(512 * 1024 * 1024 // 4, device=dev)
         samples = []
         with torch.no_grad():
@@ -383,10 +401,19 @@ def main():
     if elapsed_cached is not None:
         elapsed_cached = float(t[1].item())
     repeats = [float(v) for v in t[2:].tolist()]
-    gemm_ms = ev.elapsed_ms()
-    ev.destroy()
+    gemm_ms = []
+    if ev is not None:
+        gemm_ms = ev.elapsed_ms()
+        ev.destroy()
     path_used = layer._last_path
-    assert bool(torch.isfinite(y).all())
+    assert bool(torch.isfinite(y_last).all())
+
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        rows = torch.randperm(M_TOKENS, generator=torch.Generator().manual_seed(0))[:DUMP_ROWS].sort().values
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "y.npy"),
+                y_last.reshape(M_TOKENS, N_OUT)[rows.to(dev)].to(torch.float32).cpu().numpy())
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -398,7 +425,7 @@ def main():
         peak = PEAK["i8"] if is_i8 else (PEAK["f16"] if is_f16 else PEAK["f32"])
         traffic, traffic_source = None, None
         tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tpath):
+        if args.full and os.path.exists(tpath):
             try:
                 rec = json.load(open(tpath)).get("i8" if is_i8 else ("f16x2" if is_f16 else "f32"), {})
                 traffic = rec.get("hbm_bytes_per_launch")
@@ -416,7 +443,7 @@ def main():
         # a yardstick, not part of the product: the SAME limb products as one plain fp16 GEMM of the vendor library (torch.mm -> hipBLASLt) --
         # [q | q] . [Whi | Wlo]^T and [thi | thi | tlo] . [Bhi | Blo | Bhi]^T concatenated along K -- timed live on this box (rank 0, one GPU)
         yard = None
-        if world == 1 and is_f16 and not is_i8:
+        if args.full and world == 1 and is_f16 and not is_i8:
             try:
                 kq = 2 * K_IN + 3 * ((RANK + 63) // 64 * 64)
                 ya = torch.randint(-7, 8, (M_TOKENS, kq), device=dev).half()
@@ -448,46 +475,49 @@ def main():
                        "weights_requantized_every_step": not args.hoist_weights,
                        "flop_per_step_per_gpu": FLOP_PER_STEP, "algorithmic_bytes_per_step_per_gpu": BYTES_PER_STEP},
             "value_per_gpu": round(value / world, 1),
-            "ms_per_step_stats": {"median": round(repeats[len(repeats) // 2] / args.steps * 1e3, 4),
-                                  "min": round(repeats[0] / args.steps * 1e3, 4), "max": round(repeats[-1] / args.steps * 1e3, 4),
-                                  "repeats": len(repeats),
-                                  "note": f"{len(repeats)} further repeats of the {args.steps}-step region (max over ranks each), "
-                                          "after the region `value` is taken from"},
             "algorithmic_GBps_per_gpu": round(BYTES_PER_STEP * args.steps / elapsed / 1e9, 1),
             "frac_of_hbm_peak": round(BYTES_PER_STEP * args.steps / elapsed / 1e9 / PEAK["hbm_gbs"], 4),
             "calibration": {"ms": round(calib_ms, 2), "allreduce_elements": exchanged, "comm": args.calib_comm,
                             "allreduce_ms": (None if not exchanged else round(calibration.LAST_EXCHANGE["allreduce_ms"], 4)),
                             "note": "allreduce_ms: HIP events around the ONE data collective on rank 0 (null at one GPU: no collective)"},
-            "with_cached_weight_operands": None if elapsed_cached is None else {
-                "ms_per_step": round(elapsed_cached / args.steps * 1e3, 4),
-                "value": round(world * FLOP_PER_STEP * args.steps / elapsed_cached / 1e9, 1),
-                "note": "eval-mode module: FQ(W), FQ(A), FQ(B) operands reused while unchanged; bit-identical output"},
-            "cold_caches": None if cold_ms is None else {
-                "ms_per_step": round(cold_ms, 4), "value": round(FLOP_PER_STEP / cold_ms / 1e6, 1),
-                "note": "median of 12 single forwards, each after a 512 MB write that evicts L2 and Infinity Cache; event-timed"},
-            "roofline": {"bound": "mfma", "kernel": kernel_name,
-                         "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel_launches_timed": len(gemm_ms), "peak_dtype": peak_s, "kernel_ms_avg": round(gemm_avg_ms, 4),
-                         "frac_vs_f16_mfma_peak": round(achieved / PEAK["f16"], 4),
-                         "kernel_ms_min": round(min(gemm_ms), 4) if gemm_ms else None,
-                         "vendor_gemm_same_limb_products": yard,
-                         "frac_vs_f32_mfma_peak": round(achieved / PEAK["f32"], 4),
-                         # the contraction on its OWN flops (2MKN + 2MrN: the LoRA-down product 2MKr runs in the activation pass)
-                         "achieved_own_flops": round((FLOP_PER_STEP - 2 * M_TOKENS * K_IN * RANK) / (gemm_avg_ms * 1e-3) / 1e12, 2) if gemm_avg_ms > 0 else None,
-                         # the rest of a step: activation pass (+ weight rows) and FQ(A)^T -- HBM-bound helpers.  bytes = what they must
-                         # move (x read 4MK, levels written 2MK, t limbs 4Mr + row scales, W read 4NK + limbs written 4NK, A/B small)
-                         "helpers": (lambda hb, hms: {"ms": round(hms, 4), "bytes": hb, "GBps": round(hb / (hms * 1e-3) / 1e9, 1) if hms > 0 else None,
-                                                      "frac_of_hbm_peak": round(hb / (hms * 1e-3) / 1e9 / PEAK["hbm_gbs"], 4) if hms > 0 else None,
-                                                      "note": "ms = ms_per_step - kernel_ms_avg (launch gaps included)"})(
-                             6 * M_TOKENS * K_IN + 4 * M_TOKENS * RANK + 4 * M_TOKENS + (0 if args.hoist_weights else 8 * N_OUT * K_IN + 12 * RANK * (K_IN + N_OUT)),
-                             ms_per_step - gemm_avg_ms)},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out.update({
+                "ms_per_step_stats": {"median": round(repeats[len(repeats) // 2] / args.steps * 1e3, 4),
+                                      "min": round(repeats[0] / args.steps * 1e3, 4), "max": round(repeats[-1] / args.steps * 1e3, 4),
+                                      "repeats": len(repeats),
+                                      "note": f"{len(repeats)} further repeats of the {args.steps}-step region (max over ranks each), "
+                                              "after the region `value` is taken from"},
+                "with_cached_weight_operands": None if elapsed_cached is None else {
+                    "ms_per_step": round(elapsed_cached / args.steps * 1e3, 4),
+                    "value": round(world * FLOP_PER_STEP * args.steps / elapsed_cached / 1e9, 1),
+                    "note": "eval-mode module: FQ(W), FQ(A), FQ(B) operands reused while unchanged; bit-identical output"},
+                "cold_caches": None if cold_ms is None else {
+                    "ms_per_step": round(cold_ms, 4), "value": round(FLOP_PER_STEP / cold_ms / 1e6, 1),
+                    "note": "median of 12 single forwards, each after a 512 MB write that evicts L2 and Infinity Cache; event-timed"},
+                "roofline": {"bound": "mfma", "kernel": kernel_name,
+                             "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                             "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_source": traffic_source,
+                             "kernel_launches_timed": len(gemm_ms), "peak_dtype": peak_s, "kernel_ms_avg": round(gemm_avg_ms, 4),
+                             "frac_vs_f16_mfma_peak": round(achieved / PEAK["f16"], 4),
+                             "kernel_ms_min": round(min(gemm_ms), 4) if gemm_ms else None,
+                             "vendor_gemm_same_limb_products": yard,
+                             "frac_vs_f32_mfma_peak": round(achieved / PEAK["f32"], 4),
+                             # the contraction on its OWN flops (2MKN + 2MrN: the LoRA-down product 2MKr runs in the activation pass)
+                             "achieved_own_flops": round((FLOP_PER_STEP - 2 * M_TOKENS * K_IN * RANK) / (gemm_avg_ms * 1e-3) / 1e12, 2) if gemm_avg_ms > 0 else None,
+                             # the rest of a step: activation pass (+ weight rows) and FQ(A)^T -- HBM-bound helpers.  bytes = what they must
+                             # move (x read 4MK, levels written 2MK, t limbs 4Mr + row scales, W read 4NK + limbs written 4NK, A/B small)
+                             "helpers": (lambda hb, hms: {"ms": round(hms, 4), "bytes": hb, "GBps": round(hb / (hms * 1e-3) / 1e9, 1) if hms > 0 else None,
+                                                          "frac_of_hbm_peak": round(hb / (hms * 1e-3) / 1e9 / PEAK["hbm_gbs"], 4) if hms > 0 else None,
+                                                          "note": "ms = ms_per_step - kernel_ms_avg (launch gaps included)"})(
+                                 6 * M_TOKENS * K_IN + 4 * M_TOKENS * RANK + 4 * M_TOKENS + (0 if args.hoist_weights else 8 * N_OUT * K_IN + 12 * RANK * (K_IN + N_OUT)),
+                                 ms_per_step - gemm_avg_ms)},
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             with torch.no_grad():
                 x_lv = layer.quantizers_input[key].quantize_levels(x).cpu()
                 w_lv = layer.quantizers_weight[key].quantize_levels(layer.linear.weight.detach()).cpu()
-            out["cpu_baseline"], out["parity"] = cpu_baseline_and_parity((W, bias, A, B), calib_host, x_host, y.cpu(), x_lv, w_lv)
+            out["cpu_baseline"], out["parity"] = cpu_baseline_and_parity((W, bias, A, B), calib_host, x_host, y_last.cpu(), x_lv, w_lv)
         print(json.dumps(out), flush=True)
     if comm is not None:
         comm.destroy()

@@ -22,7 +22,10 @@ def test_layernorm_oracle_matches_reference_fixture(name):
     from oracle import ref_cpu as O
     meta, t = load_blk(name)
     for p in (4, 8, 32):
-        assert torch.equal(O.switchable_layernorm(t["x"], t[f"w_{p}"], t[f"b_{p}"], 1e-5), t[f"y_{p}"])
+        # bit-identical on the host that wrote the fixture; another CPU rounds the elementwise steps in its own way, so the
+        # bound is the one LayerNorm is held to elsewhere (helpers.cosim_block): 2e-6 |y| + 2e-6
+        y, ref = O.switchable_layernorm(t["x"], t[f"w_{p}"], t[f"b_{p}"], 1e-5).double(), t[f"y_{p}"].double()
+        assert bool(((y - ref).abs() <= 2e-6 * ref.abs() + 2e-6).all()), f"{name}/{p}: max |d| {float((y - ref).abs().max()):.3e}"
 
 
 @pytest.mark.parametrize("name", ["mlp_mm4", "mlp_mm8", "mlp_log6"])

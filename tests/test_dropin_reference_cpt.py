@@ -1,62 +1,52 @@
-"""CPU, build container only (skipped where /root/reference is absent): part2's own model assembly
-(part2_cyclic_precision_training/cpt_model.py: CPTModel -> CPTBlock -> CPTSelfAttention / CPTLinear) built on this build's
-CPTLinear, the one-name swap of INTEGRATION.md.  No quantized compute (no GPU here)."""
-import importlib
+"""CPU: part2's own model assembly (part2_cyclic_precision_training/cpt_model.py: CPTModel -> CPTBlock -> CPTSelfAttention /
+CPTLinear) as recorded in tests/golden/dropin_cpt.npz (tests/golden/make_golden_dropin.py: the reference's CPTModel built with
+seed 0, its state dict, and every CPTLinear's constructor arguments with a seeded input and its 32-bit output).  Every one of
+its CPTLinear layers, rebuilt as this build's CPTLinear with the same arguments -- the one-name swap of INTEGRATION.md -- must
+hold the same state-dict entries, load the reference's strictly, fan out set_precision() and give the reference layer's
+32-bit output.  No quantized compute (no GPU here)."""
+import json
 import os
-import sys
-import types
 
+import numpy as np
 import pytest
 import torch
 
-REF = "/root/reference/part2_cyclic_precision_training"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (only the build container has it)")
+from helpers import assert_close_y
 
-
-def _config():
-    model = types.SimpleNamespace(vocab_size=97, n_positions=32, n_embd=32, n_layer=2, n_head=4, layer_norm_epsilon=1e-5,
-                                  embd_pdrop=0.0, bit_widths=[4, 6, 32], shared_lora_rank=4, shared_lora_alpha=8,
-                                  quantizer_per_bit={4: "log", 6: "log", 32: None}, gradient_bits=8)
-    return {"model": model, "training": types.SimpleNamespace(target_bits=6)}
-
-
-def _build(swap):
-    sys.dont_write_bytecode = True
-    if REF not in sys.path:
-        sys.path.insert(0, REF)       # the reference imports its siblings by bare name (quantization, quantization_methods)
-    for name in ("cpt_model", "quantization", "quantization_methods"):
-        sys.modules.pop(name, None)
-    cm = importlib.import_module("cpt_model")
-    if swap:
-        import llm_qat_on_gpt2_amd as pkg
-        cm.CPTLinear = pkg.cpt.CPTLinear
-    torch.manual_seed(0)
-    return cm.CPTModel(_config())
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def test_reference_cpt_model_builds_on_the_dropin_layer():
     import llm_qat_on_gpt2_amd as pkg
-    try:
-        ref, mine = _build(False), _build(True)
-    finally:
-        sys.path.remove(REF)
-        for name in ("cpt_model", "quantization", "quantization_methods"):
-            sys.modules.pop(name, None)
-    layers = [m for m in mine.modules() if m.__class__.__name__ == "CPTLinear"]
-    assert len(layers) == 2 * 4 + 1 and all(isinstance(m, pkg.cpt.CPTLinear) for m in layers)      # 4 per block + lm_head
-    sd_ref, sd_mine = ref.state_dict(), mine.state_dict()
-    assert list(sd_ref.keys()) == list(sd_mine.keys())
-    assert {k: tuple(v.shape) for k, v in sd_ref.items()} == {k: tuple(v.shape) for k, v in sd_mine.items()}
-    mine.load_state_dict(sd_ref, strict=True)
-    mine.set_precision(4)
-    assert all(m.current_bits == 4 and m.quantizer_input.num_bits == 4 for m in layers)
-    mine.disable_lora_for_calibration()
-    assert all(m.calibration_mode for m in layers)
-    mine.enable_lora_after_calibration()
-    assert not any(m.calibration_mode for m in layers)
-    # the 32-bit path is plain F.linear and runs anywhere: same logits as the reference model with the same weights
-    ref.set_precision(32); mine.set_precision(32); ref.eval(); mine.eval()
-    ids = torch.randint(0, 97, (2, 16))
-    with torch.no_grad():
-        a, b = ref(ids), mine(ids)
-    assert torch.equal(a.logits, b.logits)
+    z = np.load(os.path.join(GOLDEN, "dropin_cpt.npz"), allow_pickle=False)
+    meta = json.loads(str(z["meta"]))
+    cfg = meta["config"]
+    sd_ref = {k: torch.from_numpy(z[f"p{i}"]) for i, k in enumerate(meta["keys"])}
+    layers = meta["layers"]
+    assert len(layers) == 2 * 4 + 1                                                 # 4 per block + lm_head
+    covered = set()
+    for i, lay in enumerate(layers):
+        m = pkg.cpt.CPTLinear(lay["in"], lay["out"], cfg["bit_widths"], {int(b): q for b, q in cfg["quantizer_per_bit"].items()},
+                              cfg["gradient_bits"], bias=lay["bias"], shared_lora_rank=cfg["shared_lora_rank"],
+                              shared_lora_alpha=cfg["shared_lora_alpha"])
+        assert m.__class__.__name__ == "CPTLinear"             # what the reference's calibration toggles match on
+        pre = lay["name"] + "."
+        ref_keys = [k for k in meta["keys"] if k.startswith(pre)]
+        sd_mine = m.state_dict()
+        assert ref_keys == [pre + k for k in sd_mine.keys()], lay["name"]
+        assert {k: tuple(sd_ref[k].shape) for k in ref_keys} == {pre + k: tuple(v.shape) for k, v in sd_mine.items()}, lay["name"]
+        m.load_state_dict({k[len(pre):]: sd_ref[k] for k in ref_keys}, strict=True)
+        covered.update(ref_keys)
+        m.set_precision(4)
+        assert m.current_bits == 4 and m.quantizer_input.num_bits == 4
+        with pytest.raises(ValueError):
+            m.set_precision(5)
+        # the 32-bit path is plain F.linear and runs anywhere: the reference layer's output with the same weights
+        m.set_precision(32); m.eval()
+        with torch.no_grad():
+            y = m(torch.from_numpy(z[f"x{i}"]))
+        assert_close_y(y, torch.from_numpy(z[f"y{i}"]), lay["name"])      # the project's parity bound: recorded on another host's CPU
+    # everything else in the reference's state dict belongs to the assembly itself (embeddings, LayerNorms)
+    rest = [k for k in meta["keys"] if k not in covered]
+    assert rest == ["wte.weight", "wpe.weight"] + [f"h.{b}.{ln}.{p}" for b in range(2) for ln in ("ln_1", "ln_2") for p in ("weight", "bias")] \
+        + ["ln_f.weight", "ln_f.bias"], rest

@@ -1,59 +1,53 @@
-"""CPU, build container only (skipped where /root/reference is absent, e.g. on the GPU box): the drop-in claim itself.
-The reference's own GPT-2 assembly (part1_switchable_precision/models_sp.py) is imported with its `SPLinearWithLoRA`
-replaced by this build's class -- the one-line swap of INTEGRATION.md -- and must construct, expose the same state-dict,
-fan out set_precision() and toggle calibration_mode exactly as with the reference's class.  No compute (no GPU here)."""
-import importlib
+"""CPU: the drop-in claim itself, against the reference's own GPT-2 assembly (part1_switchable_precision/models_sp.py) as
+recorded in tests/golden/dropin_sp.npz (tests/golden/make_golden_dropin.py: the reference's SPLMHeadModel built with seed 0,
+its state dict, seeded token ids and its 32-bit logits).  This build's model on the drop-in classes must expose the same
+state dict, load the reference's checkpoint strictly, fan out set_precision() and toggle calibration_mode exactly as the
+reference's model does, and give the reference's 32-bit logits.  No quantized compute (no GPU here)."""
+import json
 import os
-import sys
+from collections import OrderedDict
 
+import numpy as np
 import pytest
 import torch
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "part1_switchable_precision")),
-                                reason="reference checkout not present (only the build container has it)")
+from helpers import assert_close_y
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def _config():
+def _fixture():
+    z = np.load(os.path.join(GOLDEN, "dropin_sp.npz"), allow_pickle=False)
+    meta = json.loads(str(z["meta"]))
+    sd = OrderedDict((k, torch.from_numpy(z[f"p{i}"])) for i, k in enumerate(meta["keys"]))
+    return meta, sd, torch.from_numpy(z["ids"]), torch.from_numpy(z["logits"])
+
+
+def _config(meta):
     from transformers import GPT2Config
-    cfg = GPT2Config(vocab_size=97, n_positions=32, n_embd=32, n_layer=2, n_head=4)
-    cfg.bit_widths = [4, 6, 32]
-    cfg.lora_rank_per_bit = {4: 4, 6: 4, 32: 0}
-    cfg.lora_alpha_per_bit = {4: 4, 6: 4, 32: 0}
-    cfg.quantizer_per_bit = {4: "minmax", 6: "log", 32: None}
-    cfg.activation_bits_per_bit = {4: 4, 6: 6, 32: 32}
-    cfg.per_channel_quantization = True
-    cfg.layer_norm_epsilon = 1e-5
-    cfg.embd_pdrop = 0.0
+    cfg = GPT2Config(**meta["config"])
+    for k, v in meta["extra"].items():
+        setattr(cfg, k, {int(b): x for b, x in v.items()} if isinstance(v, dict) else v)
     return cfg
 
 
-def _build(swap):
-    sys.dont_write_bytecode = True
-    if REF not in sys.path:
-        sys.path.insert(0, REF)
-    for name in [m for m in sys.modules if m.startswith("part1_switchable_precision")]:
-        del sys.modules[name]
-    models = importlib.import_module("part1_switchable_precision.models_sp")
-    if swap:
-        import llm_qat_on_gpt2_amd as pkg
-        # what editing models_sp.py:14 (`from part1_switchable_precision.lora import SPLinearWithLoRA`) to import this
-        # build's class does: rebind the name the model code instantiates
-        models.SPLinearWithLoRA = pkg.SPLinearWithLoRA
-        if swap == "blocks":        # the LayerNorm producer and the MLP with the fused GELU as well
-            models.SwitchableLayerNorm = pkg.SwitchableLayerNorm
-            models.SPMLP = pkg.SPMLP
+def _build(meta):
+    import llm_qat_on_gpt2_amd as pkg
     torch.manual_seed(0)
-    return models.SPLMHeadModel(_config())
+    return pkg.SPLMHeadModel(_config(meta))
+
+
+def _logits(o):
+    return o if torch.is_tensor(o) else (o["logits"] if isinstance(o, dict) else o.logits)
 
 
 def test_reference_model_builds_on_the_dropin_layers():
     import llm_qat_on_gpt2_amd as pkg
-    ref = _build(swap=False)
-    mine = _build(swap=True)
+    meta, sd_ref, ids, logits_ref = _fixture()
+    mine = _build(meta)
     layers = [m for m in mine.modules() if m.__class__.__name__ == "SPLinearWithLoRA"]
     assert len(layers) == 8 and all(isinstance(m, pkg.SPLinearWithLoRA) for m in layers)      # 4 per block x 2 blocks
-    sd_ref, sd_mine = ref.state_dict(), mine.state_dict()
+    sd_mine = mine.state_dict()
     assert list(sd_ref.keys()) == list(sd_mine.keys())
     assert {k: tuple(v.shape) for k, v in sd_ref.items()} == {k: tuple(v.shape) for k, v in sd_mine.items()}
     mine.load_state_dict(sd_ref, strict=True)                                               # reference checkpoint loads
@@ -68,14 +62,11 @@ def test_reference_model_builds_on_the_dropin_layers():
     assert all(m.calibration_mode for m in layers)
     mine.enable_lora_after_calibration()
     assert not any(m.calibration_mode for m in layers)
-    # the teacher path (32 bit) is plain F.linear and runs anywhere: same logits as the reference model with the same weights
-    ref.set_precision(32); ref.eval(); mine.eval()
-    ids = torch.randint(0, 97, (2, 16))
+    # the teacher path (32 bit) is plain F.linear and runs anywhere: the reference model's logits with the same weights
+    mine.eval()
     with torch.no_grad():
-        out_ref, out_mine = ref(ids), mine(ids)
-    lr = out_ref["logits"] if isinstance(out_ref, dict) else (out_ref.logits if hasattr(out_ref, "logits") else out_ref[0])
-    lm = out_mine["logits"] if isinstance(out_mine, dict) else (out_mine.logits if hasattr(out_mine, "logits") else out_mine[0])
-    assert torch.allclose(lr, lm, atol=1e-6)
+        lm = _logits(mine(ids))
+    assert_close_y(lm, logits_ref, "32-bit logits")                 # the project's parity bound: recorded on another host's CPU
     # below 32 bits the layers are HIP-only: a CPU tensor is refused loudly instead of silently falling back
     mine.set_precision(4)
     for m in layers:
@@ -86,22 +77,19 @@ def test_reference_model_builds_on_the_dropin_layers():
 
 
 def test_reference_model_builds_on_the_dropin_block_pieces():
-    """The same with SwitchableLayerNorm and SPMLP swapped too: identical state dict, reference checkpoint loads, identical
-    32-bit logits (the teacher path is plain torch)."""
+    """The same with SwitchableLayerNorm and SPMLP: identical state dict, reference checkpoint loads, the reference's 32-bit
+    logits (the teacher path is plain torch)."""
     import llm_qat_on_gpt2_amd as pkg
-    ref = _build(swap=False)
-    mine = _build(swap="blocks")
+    meta, sd_ref, ids, logits_ref = _fixture()
+    mine = _build(meta)
     assert sum(isinstance(m, pkg.SwitchableLayerNorm) for m in mine.modules()) == 2 * 2 + 1
     assert sum(isinstance(m, pkg.SPMLP) for m in mine.modules()) == 2
-    sd_ref, sd_mine = ref.state_dict(), mine.state_dict()
+    sd_mine = mine.state_dict()
     assert list(sd_ref.keys()) == list(sd_mine.keys())
     mine.load_state_dict(sd_ref, strict=True)
     assert mine.set_precision(4) == 4
     assert all(m.current_precision == 4 for m in mine.modules() if isinstance(m, pkg.SwitchableLayerNorm))
-    ref.set_precision(32); mine.set_precision(32); ref.eval(); mine.eval()
-    ids = torch.randint(0, 97, (2, 16))
+    mine.set_precision(32); mine.eval()
     with torch.no_grad():
-        a, b = ref(ids), mine(ids)
-    pick = lambda o: o["logits"] if isinstance(o, dict) else (o.logits if hasattr(o, "logits") else (o if torch.is_tensor(o) else o[0]))
-    assert torch.equal(pick(a), pick(b))
-
+        lm = _logits(mine(ids))
+    assert_close_y(lm, logits_ref, "32-bit logits")                 # the project's parity bound: recorded on another host's CPU
