@@ -109,12 +109,14 @@ size_t fwd_f16x2_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t r, int
   return make_layout(M, K, r, N, path == SPQ_PATH_F16X3 ? 2 : path == SPQ_PATH_I8 ? -1 : 1).total;
 }
 
-// power of two p with  v_max * p  in [2^13, 2^14)   (p = 1 for v_max == 0 or non-finite)
+// power of two p with  v_max * p  in [2^13, 2^14)   (p = 1 for v_max == 0 or non-finite).  p is capped at 2^126 (1/p stays a
+// normal float): a row whose largest value is below 2^-113 -- e.g. an input row of tiny subnormals times the LoRA-A factor --
+// would otherwise get p = inf, 1/p = 0 and a NaN row (0 * inf); under the cap its values are only smaller than 2^13
 __device__ __forceinline__ float pow2_scale_for(float vmax) {
   if (!(vmax > 0.f) || !(vmax < INFINITY)) return 1.f;
   int ex;
   (void)frexpf(vmax, &ex);            // vmax = f * 2^ex, f in [0.5, 1)
-  return ldexpf(1.f, 14 - ex);
+  return ldexpf(1.f, min(14 - ex, 126));
 }
 
 // =================================================================================================
