@@ -320,3 +320,102 @@ def tie_matrix(bits, sym, chan, regions=REGIONS, rows=None, seed=0, **kw):
     mins = np.array([p[0] for p in params], dtype=np.float32)
     ranges = np.array([p[1] for p in params], dtype=np.float32)
     return X, mins, ranges, np.array(reg)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# two-limb fp16 operands (split2 in spq_f16x2.hip) and what can be read back through them
+# ---------------------------------------------------------------------------------------------------------------------------
+def split2(v):
+    """split2 (spq_f16x2.hip) in numpy: hi = RN_f16(v), lo = RN_f16(v - hi), the difference taken in float32."""
+    v = _f32(v)
+    with np.errstate(over="ignore", invalid="ignore"):
+        hi = v.astype(np.float16)
+        lo = (v - hi.astype(np.float32)).astype(np.float32).astype(np.float16)
+    return hi, lo
+
+
+def limb_decode(hi, lo, descale):
+    """(hi + lo) * descale in float64 (exact: the limbs and the power-of-two descale lose nothing there)."""
+    return (np.asarray(hi).astype(np.float64) + np.asarray(lo).astype(np.float64)) * np.asarray(descale, dtype=np.float64)
+
+
+def limb_tol(v, descale):
+    """What two fp16 limbs of v / descale, decoded, may be off by: 2^-22 |v| from the two roundings, plus half an f16 subnormal
+    step of lo (2^-25 before the descale), both with a 2x margin -- and room for the 1-ulp (2^-23) exp2 of the device."""
+    return np.abs(np.asarray(v, np.float64)) * 2.0 ** -21 + np.asarray(descale, dtype=np.float64) * 2.0 ** -24
+
+
+def separable(x, q_ref, o_ref, log_min, log_range, bits, sym, direct=False, tol=None, scale=1.0):
+    """Elements whose neighbouring levels dequantise (times `scale`) more than 2 * tol away from their own value -- there a
+    read-back within tol pins the level.  tol=None: 2 float32 ulps (a value read back in fp32 within 1 ulp)."""
+    _, qlo, qhi = level_range(bits, sym)
+    ok = np.ones(np.shape(x), bool)
+    for dq in (-1, 1):
+        qn = np.clip(q_ref + dq, qlo, qhi)
+        o_n = (dequant(x, qn, log_min, log_range, bits, sym, direct) * _f32(scale)).astype(np.float32)
+        if tol is None:
+            far = ulp_distance(o_n, o_ref) > 2
+        else:
+            far = np.abs(o_n.astype(np.float64) - np.asarray(o_ref, np.float64)) > 2 * tol
+        ok &= (qn == q_ref) | far
+    return ok
+
+
+def ulp_pow2(v):
+    """The float32 ulp of v: a power of two (v finite, normal, non-zero)."""
+    _, e = np.frexp(np.abs(_f32(v)).astype(np.float64))
+    return np.ldexp(1.0, e - 24).astype(np.float32)
+
+
+def bias_ties(bits, sym, chan, regions=("R1", "R4"), min_lg=None, max_lg=24.0, signed=True, seed=0):
+    """Per-channel quantizers and a value on one rounding tie of each, for a store that computes y = bias + q * s with an
+    integer q: returns (bias, s, log_min, log_range) with bias[c] the float nearest 2^lg* of a tie of channel c and
+    s[c] = ulp(bias[c]), so that q = -Q .. Q walks bias over its +-Q float neighbours.  Ties are picked at random among those
+    with min_lg <= lg* <= max_lg (R1's channels: the tie at lg = 0, i.e. |x| = 1 exactly, when that is in the window); signs
+    alternate when `signed`."""
+    rng = np.random.default_rng(seed)
+    per = {r: iter(region_params(r, bits, sym, -(-chan // len(regions)), seed + 11 * j)) for j, r in enumerate(regions)}
+    _, qlo, qhi = level_range(bits, sym)
+    ts = float(qlo) + 0.5 + np.arange(int(qhi - qlo), dtype=np.float64)
+    lo = -120.0 if min_lg is None else float(min_lg)
+    bias, mins, ranges = np.empty(chan, np.float32), np.empty(chan, np.float32), np.empty(chan, np.float32)
+    for c in range(chan):
+        reg = regions[c % len(regions)]
+        m, R = next(per[reg])
+        lgs = _tie_lg(ts, m, R, bits, sym)
+        ok = np.nonzero((lgs >= lo) & (lgs <= max_lg))[0]
+        if len(ok) == 0:                                         # shift the quantizer so that its lowest tie is in the window
+            m = F32(float(m) + (lo - lgs.min()) + 0.25)
+            lgs = _tie_lg(ts, m, R, bits, sym)
+            ok = np.nonzero((lgs >= lo) & (lgs <= max_lg))[0]
+        at0 = ok[np.abs(lgs[ok]) < 1e-9]
+        lg = lgs[at0[0]] if (reg == "R1" and len(at0)) else lgs[rng.choice(ok)]
+        b = np.float32(np.exp2(lg))
+        bias[c] = -b if (signed and c % 2) else b
+        mins[c], ranges[c] = m, R
+    return bias, ulp_pow2(bias), mins, ranges
+
+
+def walk(bias, s, Q):
+    """float32(bias + q * s) for q = -Q .. Q (rows) -- the store's y when q * s is exact."""
+    q = np.arange(-Q, Q + 1, dtype=np.float32)[:, None]
+    return (q * s[None, :]).astype(np.float32) + bias[None, :]
+
+
+def ln_ties(bits, sym, K, M, c=4.0, seed=0, **kw):
+    """A LayerNorm whose output walks rounding ties: bias[k] sits on a tie of column k's quantizer (`bias_ties`) and
+    weight[k] = c * ulp(bias[k]), so weight * n + bias = bias + j ulps with j ~ round(c * n) for the normalised n of a
+    standard-normal row -- on the tie for |n| < 1/(2c) and on its neighbours elsewhere.  Returns (x [M, K], weight, bias,
+    log_min, log_range)."""
+    bias, s, mins, ranges = bias_ties(bits, sym, K, seed=seed, **kw)
+    x = np.random.default_rng(seed).standard_normal((M, K)).astype(np.float32)
+    return x, (F32(c) * s).astype(np.float32), bias, mins, ranges
+
+
+def layernorm(x, weight, bias, eps=1e-5):
+    """weight * ((x - mean) / sqrt(var + eps)) + bias with float64 statistics and the last two operations in float32 -- the
+    kernel's statistics differ in the last bits (summation order); for constructing inputs, not as a bit-exact reference."""
+    x64 = np.asarray(x, np.float64)
+    mean = x64.mean(axis=-1, keepdims=True)
+    n = ((x64 - mean) / np.sqrt(x64.var(axis=-1, keepdims=True) + eps)).astype(np.float32)
+    return ((_f32(weight) * n).astype(np.float32) + _f32(bias)).astype(np.float32)

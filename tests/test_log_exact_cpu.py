@@ -110,3 +110,80 @@ def test_ulp_distance():
     a = np.array([1.0, -0.0, 1.0, np.nan], np.float32)
     b = np.array([np.nextafter(np.float32(1), np.float32(2)), 0.0, np.float32(1), np.nan], np.float32)
     assert L.ulp_distance(a, b).tolist() == [1, 0, 0, 0]
+
+
+def test_split2_emulation_and_limb_decoder():
+    """split2's two roundings, emulated in numpy, decode to within limb_tol -- across binades, at f16 subnormals of lo and hi,
+    and at the largest value a power-of-two row scale allows (2^14)."""
+    rng = np.random.default_rng(1)
+    v = np.concatenate([rng.uniform(-1, 1, 20000) * np.exp2(rng.integers(-40, 14, 20000)),
+                        [0.0, -0.0, 2.0 ** -24, 2.0 ** -30, 16383.99, -8192.0, 1.0 + 2.0 ** -23]]).astype(np.float32)
+    hi, lo = L.split2(v)
+    assert hi.dtype == np.float16 and lo.dtype == np.float16
+    d = L.limb_decode(hi, lo, 1.0)
+    assert (np.abs(d - v) <= L.limb_tol(v, 1.0)).all()
+    # hi is RN_f16(v), lo takes the float32 residual: exact whenever the residual fits 11 bits
+    assert (hi == v.astype(np.float16)).all()
+    w = (hi.astype(np.float32) + np.float32(2.0 ** -12) * np.sign(v)).astype(np.float32)   # residual of one bit
+    h2, l2 = L.split2(w)
+    assert (L.limb_decode(h2, l2, 1.0) == w).all()
+    # a descale multiplies out exactly; without the absolute floor the decoder's bound would fail at subnormal lo
+    d2 = L.limb_decode(hi, lo, 2.0 ** -20)
+    assert (np.abs(d2 - v.astype(np.float64) * 2.0 ** -20) <= L.limb_tol(v.astype(np.float64) * 2.0 ** -20, 2.0 ** -20)).all()
+    assert (np.abs(d - v) > np.abs(v.astype(np.float64)) * 2.0 ** -21).any()
+
+
+@pytest.mark.parametrize("bits,sym,direct", [(3, True, False), (8, True, False), (12, False, False), (18, False, True)])
+def test_limb_construction_reaches_the_floors(bits, sym, direct):
+    """A tie matrix per output row (the weight-preparation tests' W = tie_matrix^T) keeps >= 100 exact ties and >= 1000 within the
+    device bound among the elements that two fp16 limbs under a power-of-two row scale can still tell apart."""
+    X, m, R, _ = L.tie_matrix(bits, sym, 48, rows=768, seed=bits)
+    W = np.ascontiguousarray(X.T)
+    q = L.levels(W, m[:, None], R[:, None], bits, sym)
+    o = L.dequant(W, q, m[:, None], R[:, None], bits, sym, direct)
+    rmax = np.abs(o).max(axis=1)
+    _, e = np.frexp(rmax)
+    rs = np.where(rmax > 0, np.ldexp(1.0, -np.minimum(14 - e, 126)), 1.0)       # pow2_scale_for: row max * 2^e in [2^13, 2^14)
+    hi, lo = L.split2((o / rs[:, None]).astype(np.float32))
+    tol = L.limb_tol(o, rs[:, None])
+    assert (np.abs(L.limb_decode(hi, lo, rs[:, None]) - o) <= tol).all()
+    sep = L.separable(W, q, o, m[:, None], R[:, None], bits, sym, direct, tol=tol)
+    exact, near = L.coverage(np.where(sep, W, np.float32(np.nan)), m[:, None], R[:, None], bits, sym)
+    assert exact >= 100 and near >= 1000, (exact, near)
+
+
+@pytest.mark.parametrize("bits,sym,min_lg", [(4, True, None), (8, False, None), (16, True, None), (8, True, 3.0), (13, False, 3.0)])
+def test_bias_construction_reaches_the_floors(bits, sym, min_lg):
+    """bias_ties + walk: y = bias + q ulp(bias) lands on and around a tie of every channel; with min_lg = 3 (the GELU store's
+    window, where gelu is the identity in fp32) every y is above 8.  Decoded through limbs under one 2^-G, the floors hold."""
+    bias, s, m, R = L.bias_ties(bits, sym, 512, min_lg=min_lg, max_lg=20.0, signed=min_lg is None, seed=bits)
+    assert (s == L.ulp_pow2(bias)).all() and (np.log2(s) == np.round(np.log2(s))).all()
+    y = L.walk(bias, s, 127)
+    np.testing.assert_array_equal(y[127], bias)
+    assert (np.unique(y.view(np.int32), axis=0).shape[0]) == 255                  # 255 distinct rows: the neighbours
+    if min_lg is not None:
+        assert (y > 8.0).all()
+    q = L.levels(y, m[None], R[None], bits, sym)
+    o = L.dequant(y, q, m[None], R[None], bits, sym)
+    G = 13 - int(np.ceil(np.log2(np.abs(o).max())))
+    tol = L.limb_tol(o, 2.0 ** -G)
+    sep = L.separable(y, q, o, m[None], R[None], bits, sym, tol=tol)
+    exact, near = L.coverage(np.where(sep, y, np.float32(np.nan)), m[None], R[None], bits, sym)
+    assert exact >= 100 and near >= 1000, (exact, near)
+    assert int(L.ambiguous(y, m[None], R[None], bits, sym).sum()) <= 4
+
+
+@pytest.mark.parametrize("K,bits,sym", [(128, 4, True), (128, 8, False), (256, 12, True), (128, 16, False), (128, 6, True)])
+def test_layernorm_construction_reaches_the_floors(K, bits, sym):
+    """ln_ties: bias on a tie of each column, weight a few ulps of it -- the normalised rows land on and around the ties, and the
+    floors hold among the elements the activation pass's limbs (2^-20 relative, 2^-36 of the largest value) can tell apart."""
+    x, w, b, m, R = L.ln_ties(bits, sym, K, 2048, seed=K + bits, max_lg=20.0)
+    y = L.layernorm(x, w, b)
+    steps = np.rint((y - b[None]) / L.ulp_pow2(b)[None])
+    assert np.abs(steps).max() <= 24 and (steps == 0).mean() > 0.05                # y = bias + a few ulps, often bias itself
+    q = L.levels(y, m[None], R[None], bits, sym)
+    o = L.dequant(y, q, m[None], R[None], bits, sym)
+    tol = np.abs(o) * 2.0 ** -20 + np.exp2(np.max(m.astype(np.float64) + R)) * 2.0 ** -36
+    sep = L.separable(y, q, o, m[None], R[None], bits, sym, tol=tol)
+    exact, near = L.coverage(np.where(sep, y, np.float32(np.nan)), m[None], R[None], bits, sym)
+    assert exact >= 100 and near >= 1000, (exact, near)
