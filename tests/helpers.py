@@ -166,3 +166,80 @@ def cosim_block(blk, bits, x_gpu, affected_in=None, tol=1e-5, x_ref=None):
             aff = aff | f
         y_ref = xr2 + ol["mlp.c_proj"].forward(r6)
     return y, y_ref, aff, nflip
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Batch census: where do a block's rows come out differently when the batch is split (data-parallel replicas see exactly this)?
+# `batch_census` runs the block's stages on the full batch and on the parts whose concatenation is the same rows (as the split
+# run computed them) and compares every stage's output row by row.  A library stage (LayerNorm, a quantized linear, the residual
+# add) whose input rows are bit-identical must give bit-identical output rows; the one exception is a linear whose split-K factor
+# (spq_debug_split_k) differs between the two token counts, whose rows must then be within 5e-6.  For the attention core the
+# "same input" of a token is the same causal prefix of its sequence; a difference there is torch's, not the library's.  Every
+# differing row is attributed to the stage where it first appeared on identical input, or to a differing input (propagated: a
+# last-bit difference upstream that moved a quantisation level, or a difference earlier in the sequence).
+# ---------------------------------------------------------------------------------------------------------------------
+def _row_diff(a, b):
+    """bool [B, T]: rows (last dim) not bit-identical"""
+    return (a != b).any(dim=-1)
+
+
+def batch_census(blk, bits, x_full, x_parts, split_k=None, path=2):
+    """x_full [B, T, E]; x_parts: tensors whose concatenation over dim 0 has x_full's shape.  split_k: None -> the library's
+    current switches (spq_debug_split_k).  Returns (y_full, y_split, info): info["differ"][stage] bool [B, T] rows whose output
+    differs, info["new"][stage] the subset whose input was identical (the stage's own contribution), info["split"][stage] the
+    (S full, S part) of each linear, info["source"] bool [B, T] masks keyed "split-K <stage>", "torch attention", "propagated"."""
+    import llm_qat_on_gpt2_amd as pkg
+    lib = pkg._lib.load()
+    B_, T_, E = x_full.shape
+    lins = {"attn.c_attn": blk.attn.c_attn, "attn.c_proj": blk.attn.c_proj, "mlp.c_fc": blk.mlp.c_fc, "mlp.c_proj": blk.mlp.c_proj}
+
+    def stages(x):
+        out = {}
+        with torch.no_grad():
+            out["ln_1"] = p1 = blk.ln_1(x)
+            out["attn.c_attn"] = p2 = blk.attn.c_attn(p1)
+            out["attention core"] = p3 = blk.attn.core(p2)
+            out["attn.c_proj"] = p4 = blk.attn.c_proj(p3)
+            out["residual 1"] = x2 = x + p4
+            out["ln_2"] = p5 = blk.ln_2(x2)
+            out["mlp.c_fc"] = p6 = blk.mlp.c_fc(p5, activation="gelu")
+            out["mlp.c_proj"] = p7 = blk.mlp.c_proj(p6)
+            out["residual 2"] = x2 + p7
+            assert torch.equal(blk(x), out["residual 2"]), "the block's real (fused) forward differs from its staged run"
+        return out
+    full = stages(x_full)
+    parts = [stages(p) for p in x_parts]
+    split = {k: torch.cat([p[k] for p in parts]) for k in full}
+    inputs = {"ln_1": ("x",), "attn.c_attn": ("ln_1",), "attention core": ("attn.c_attn",), "attn.c_proj": ("attention core",),
+              "residual 1": ("x", "attn.c_proj"), "ln_2": ("residual 1",), "mlp.c_fc": ("ln_2",), "mlp.c_proj": ("mlp.c_fc",),
+              "residual 2": ("residual 1", "mlp.c_proj")}
+    full["x"], split["x"] = x_full, torch.cat(list(x_parts))
+    diff = {k: _row_diff(full[k], split[k]) for k in full}
+    info = {"differ": {}, "new": {}, "split": {}, "source": {}}
+    src_prop = torch.zeros(B_, T_, dtype=torch.bool, device=x_full.device)
+    for st, ins in inputs.items():
+        same_in = ~torch.stack([diff[i] for i in ins]).any(dim=0)
+        if st == "attention core":
+            same_in = torch.cummin(same_in.to(torch.int8), dim=1).values.bool()        # the whole causal prefix is identical
+        new = diff[st] & same_in
+        info["differ"][st], info["new"][st] = diff[st], new
+        src_prop |= diff[st] & ~same_in
+        if st in lins:
+            m = lins[st]
+            Ms = [p.shape[0] * p.shape[1] for p in x_parts]
+            S = [lib.spq_debug_split_k(M, m.in_features, m.out_features, 0 if m.calibration_mode else m.lora_rank_per_bit[bits], path)
+                 for M in [B_ * T_] + Ms]
+            if st == "mlp.c_fc":
+                S = [1] * len(S)                                        # the GELU epilogue never splits
+            info["split"][st] = tuple(S)
+            if bool(new.any()):
+                assert len(set(S)) > 1, f"{st}: {int(new.sum())} rows differ between batch sizes on identical input at equal split-K factor {S[0]}"
+                assert_close_y(split[st][new], full[st][new], f"{st}: rows on identical input, split-K {S}", 5e-6)
+                info["source"][f"split-K {st}"] = new
+        elif st == "attention core":
+            if bool(new.any()):
+                info["source"]["torch attention"] = new
+        else:
+            assert not bool(new.any()), f"{st}: {int(new.sum())} rows differ between batch sizes on identical input"
+    info["source"]["propagated"] = src_prop
+    return full["residual 2"], split["residual 2"], info

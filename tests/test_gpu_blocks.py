@@ -196,8 +196,8 @@ def test_layernorm_inside_the_activation_pass_block(pkg, name):
 
 
 @pytest.mark.parametrize("M,K,N,r,bits,qtype,pc", [
-    (8192, 768, 2304, 64, 4, "minmax", True),       # ln_1 -> c_attn of GPT-2-small, 16-row activation kernel
-    (32768, 768, 3072, 64, 4, "minmax", True),      # ln_2 -> c_fc at BASELINE config 3's 32 x 1024 tokens: 32-row panel kernel
+    (8192, 768, 2304, 64, 4, "minmax", True),       # ln_1 -> c_attn of GPT-2-small; 32-row streaming workgroups once (M + 31) / 32 >= CUs (256)
+    (32768, 768, 3072, 64, 4, "minmax", True),      # ln_2 -> c_fc at BASELINE config 3's 32 x 1024 tokens: 32-row streaming workgroups
     (4096, 1024, 4096, 64, 6, "log", True),         # GPT-2-medium dims, log quantizer: two-limb activations
     (4096, 768, 768, 16, 8, "minmax", False),       # per-tensor scale: int8 operand path
     (1000, 256, 512, 0, 4, "minmax", True),         # ragged M, no LoRA

@@ -218,18 +218,17 @@ def test_gpt2_small_stack_properties_at_full_width(pkg):
         assert y.shape == (8, T, E) and bool(torch.isfinite(y).all())
         assert all(m._last_path == pkg._lib.PATH_F16X2 for m in layers)          # the MFMA limb path ran in every layer
         assert torch.equal(model(ids), y)                                       # determinism
-        # batch-split invariance: sequences are independent (replicas over the batch see exactly this).  With SPQ_SPLIT_K=0: the
-        # split-K form of the contraction (mlp c_proj: 384 tiles at 8 x 1024 tokens, 192 at 4 x 1024) re-associates the fp32 sums
-        # by tile count, and a last-bit difference there flips levels further down the stack.
-        pkg._lib.set_switch("SPQ_SPLIT_K", "0")
+        # batch-split invariance: sequences are independent (replicas over the batch see exactly this).  The census explains every
+        # row that differs between batch 8 and 2 x batch 4, block by block and stage by stage (helpers.batch_census): a library
+        # stage on identical input rows must give identical rows, except a linear whose split-K factor differs between 8192 and
+        # 4096 tokens (mlp.c_proj under the default switches).
+        old = os.environ.get("SPQ_SPLIT_K")
         try:
-            y0 = model(ids)
-            halves = torch.cat([model(ids[:4]), model(ids[4:])])
+            for mode in ("0", None):
+                pkg._lib.set_switch("SPQ_SPLIT_K", mode)
+                _batch_split_census(pkg, model, ids, bits, mode)
         finally:
-            pkg._lib.set_switch("SPQ_SPLIT_K", None)
-        rms = float(y0.pow(2).mean().sqrt())
-        bad = ((halves - y0).abs() > 1e-5 * y0.abs() + 1e-5 * rms).any(dim=-1)
-        assert float(bad.float().mean()) <= 0.01, f"{int(bad.sum())} token rows differ between batch 8 and 2 x batch 4"
+            pkg._lib.set_switch("SPQ_SPLIT_K", old)
         # precision switching 4 -> 32 -> 4 (part4 switches before every forward)
         model.set_precision(32)
         y32 = model(ids)
@@ -239,3 +238,43 @@ def test_gpt2_small_stack_properties_at_full_width(pkg):
         # random-weight 4-bit students are lossy (no training here); the output must still be of the teacher's scale
         ratio = float(y.pow(2).mean().sqrt()) / float(y32.pow(2).mean().sqrt())
         assert 0.2 < ratio < 5.0, ratio
+
+
+# Measured on MI355X (8 x 1024 tokens vs 2 x 4 x 1024, the model above), per block: with SPQ_SPLIT_K=0 no row differs in any bit.
+# Under the default switches mlp.c_proj takes S = 2 at 8192 tokens and S = 3 at 4096: every row of block 0's output differs in
+# the last bits (within 5e-6, checked by the census), none by more than 1e-5; downstream those bits move quantisation levels
+# and, through the attention, later tokens: 14 % of the rows are outside 1e-5 after block 1, 98 % after block 11.
+AFFECTED_BOUND = {"0": 0.0, None: 1.0}          # rows that differ in any bit (the runs are deterministic)
+FLIPPED_BOUND = {"0": 0.0, None: 0.99}          # rows outside 1e-5 |y| + 1e-5 rms(y)
+
+
+def _batch_split_census(pkg, model, ids, bits, mode):
+    from helpers import batch_census
+    half = ids.shape[0] // 2
+    with torch.no_grad():
+        pos = torch.arange(0, ids.shape[1], dtype=torch.long, device=ids.device).unsqueeze(0)
+        h_full = model.drop(model.wte(ids) + model.wpe(pos))
+        h_split = h_full.clone()
+        sources, fractions, flipped = {}, [], []
+        for i, blk in enumerate(model.h):
+            h_full, h_split, info = batch_census(blk, bits, h_full, [h_split[:half], h_split[half:]])
+            affected = (h_full != h_split).any(dim=-1)
+            fractions.append(float(affected.float().mean()))
+            flipped.append(float(rows_outside(h_split, h_full).float().mean()))     # beyond the last bits: a level moved
+            for k, m in info["source"].items():
+                if k != "propagated" and bool(m.any()):
+                    sources.setdefault(k, []).append((i, int(m.sum())))
+            if mode == "0":
+                assert not any(k.startswith("split-K") for k in info["source"] if bool(info["source"][k].any())), info["split"]
+        y_full, y_split = model.ln_f(h_full), model.ln_f(h_split)
+        assert torch.equal(model(ids), y_full)
+        assert torch.equal(torch.cat([model(ids[:half]), model(ids[half:])]), y_split)
+    print(f"SPQ_SPLIT_K={mode}: rows that differ per block {['%.5f' % f for f in fractions]}; outside 1e-5 "
+          f"{['%.5f' % f for f in flipped]}; first differences {sources}; model output rows that differ: "
+          f"{int((y_full != y_split).any(dim=-1).sum())}, outside 1e-5: {int(rows_outside(y_split, y_full).sum())}")
+    if "torch attention" not in sources and not any(k.startswith("split-K") for k in sources):
+        assert torch.equal(y_full, y_split)
+    if mode is None:
+        assert any(k == "split-K mlp.c_proj" for k in sources), "the default switches split mlp.c_proj differently at 8192 and 4096 tokens"
+    assert max(fractions) <= AFFECTED_BOUND[mode], (mode, fractions)
+    assert flipped[0] == 0.0 and max(flipped) <= FLIPPED_BOUND[mode], (mode, flipped)
