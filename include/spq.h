@@ -53,10 +53,23 @@ enum spq_path {
   SPQ_PATH_F16X3 = 4, /* any input quantizer (log, asymmetric, >12 bit) or none at all (quantize_input = 0: plain fp32
                          activations, e.g. a gradient): FQ(x)*2^G as two fp16 limbs x 2-limb weights, three f16 MFMA
                          products per algorithmic product; operands prepared with sx = 1 (no scale folding) */
-  SPQ_PATH_I8 = 5     /* int8 matrix cores (2x the f16 rate), ONE product per algorithmic product: symmetric minmax input
+  SPQ_PATH_I8 = 5,    /* int8 matrix cores (2x the f16 rate), ONE product per algorithmic product: symmetric minmax input
                          quantizer of <= 8 bits with a PER-TENSOR scale (it then leaves the sum) and symmetric minmax weights
                          of <= 8 bits: y = (sw[n] * sx) * sum_k q[m,k] wq[n,k], the integer sum exact in i32; LoRA-up stays on
                          fp16 limbs.  (The reference's evaluation loader forces per-tensor scales: deploy.py:210,238.) */
+  SPQ_PATH_FP6 = 6    /* FP6 (e2m3) operands on v_mfma_scale_f32_16x16x128_f8f6f4: exact integer levels x FIVE radix-32 digit planes of
+                         the 25-bit integer weight rint(FQ(W)[n,k] sx[k] 2^E[n]); LoRA-up stays on fp16 limbs.  Valid when the input
+                         quantizer is symmetric minmax with 2..4 bits (per-channel or per-tensor scale), lora_on_fq_input is not set,
+                         the epilogue is NONE or GELU, there is no levels-out store, rank <= 128; never split along K.  Any other
+                         request returns SPQ_ERR_UNSUPPORTED (spq_last_error names the reason) before any launch.
+                         Where the operands live (one packed plane = [rows / 32][ceil(K/128)][3072 B], the layout at the top of
+                         csrc/spq_fp6_kernel.h, numpy reference tests/fp6_ref.py):
+                           activations: the level plane of ceil(M/256)*256 rows starts at byte 0 of `workspace` after the activation stage;
+                           weights:     w_prep = [5 digit planes of Np = ceil(N/128)*128 rows, least significant first]
+                                                 [LoRA-B hi limbs Np x Rp fp16][lo limbs][Np floats 2^(E[n] - eb[n])], Rp = ceil(r/64)*64, each
+                                                 section padded to 256 B; w_rowscale[n] = 2^-E[n] with
+                                                 2^23 <= max_k |W'[n,k]| 2^E[n] < 2^24 (E = 0 for an all-zero row; NaN for a row
+                                                 that holds a non-finite element or exceeds 2^150: its output column is then NaN). */
 };
 
 enum spq_epilogue { SPQ_EPILOGUE_NONE = 0, SPQ_EPILOGUE_GELU = 1 };
@@ -189,7 +202,8 @@ typedef struct spq_prepare_args {
   const float* sx; int x_per_channel;
   void* w_prep; size_t w_prep_bytes; float* w_rowscale; float* a_prep;
   int path;  /* 0 / SPQ_PATH_F16X2 / U8X2 / F16X3: two fp16 limb planes (w_prep of spq_prep_f16x2_bytes());
-                SPQ_PATH_I8: the int8 plane of weight levels (w_prep of spq_prep_bytes(N, K, r, path)) */
+                SPQ_PATH_I8: the int8 plane of weight levels (w_prep of spq_prep_bytes(N, K, r, path));
+                SPQ_PATH_FP6: row exponents, five packed digit planes and the LoRA-B limbs (w_prep of spq_prep_bytes(N, K, r, path)) */
 } spq_prepare_args;
 
 typedef struct spq_fwd_args {

@@ -17,7 +17,8 @@ EPILOGUE_NONE, EPILOGUE_GELU = 0, 1
 COMM_ID_BYTES = 128
 LIMB_SCALE_WORKSPACE_BYTES = 16384
 PATH_AUTO, PATH_F32, PATH_F16X2, PATH_F16X3, PATH_I8 = 0, 1, 2, 4, 5    # (3: the former byte-level path, tools/variants/gemm_u8x2.h)
-PATH_NAMES = {1: "f32", 2: "f16x2", 4: "f16x3", 5: "i8"}
+PATH_FP6 = 6                                                             # FP6 (e2m3) levels x five digit planes, 2..4-bit min-max inputs
+PATH_NAMES = {1: "f32", 2: "f16x2", 4: "f16x3", 5: "i8", 6: "fp6"}
 LOG_DIRECT = 2
 QTYPE_CODE = {"minmax": MINMAX, "log": LOG}            # part1 quantizers
 QTYPE_CODE_CPT = {"minmax": MINMAX, "log": LOG_DIRECT}  # part2 quantizers (log without the level round trip)

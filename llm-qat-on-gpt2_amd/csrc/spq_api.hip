@@ -28,6 +28,7 @@ int launch_gemm_f32_nt(const float* A, int64_t lda, const float* B, int64_t ldb,
                        int64_t lda2, const float* B2, int64_t ldb2, int64_t K2, float alpha2,
                        const float* bias, float* C, int64_t ldc, int64_t M, int64_t N, hipStream_t st);
 int fwd_f16x2(const spq_fwd_args* a, hipStream_t st);
+int fp6_validate(const spq_fwd_args* a);
 size_t fwd_f16x2_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t r, int path);
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -60,7 +61,7 @@ extern "C" int spq_device_arch(char* buf, int buflen) {
 
 extern "C" size_t spq_fwd_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t r, int path) {
   if (M <= 0 || K <= 0 || N <= 0 || r < 0) return 0;
-  if (path == SPQ_PATH_F16X2 || path == SPQ_PATH_U8X2 || path == SPQ_PATH_F16X3 || path == SPQ_PATH_I8)
+  if (path == SPQ_PATH_F16X2 || path == SPQ_PATH_U8X2 || path == SPQ_PATH_F16X3 || path == SPQ_PATH_I8 || path == SPQ_PATH_FP6)
     return fwd_f16x2_workspace_bytes(M, K, N, r, path);
   // F32 path: fake-quantised activations [M,K] + low-rank intermediate [M,r]
   return align_up((size_t)M * K * sizeof(float), 256) + align_up((size_t)M * (size_t)r * sizeof(float), 256) + 256;
@@ -70,6 +71,7 @@ extern "C" int spq_linear_lora_fwd(const spq_fwd_args* a, spq_stream_t stream) {
   SPQ_REQUIRE(a, "spq_linear_lora_fwd: null args");
   SPQ_REQUIRE(a->M > 0 && a->K > 0 && a->N > 0 && a->r >= 0, "spq_linear_lora_fwd: bad shape M=%lld K=%lld N=%lld r=%lld",
               (long long)a->M, (long long)a->K, (long long)a->N, (long long)a->r);
+  if (a->path == SPQ_PATH_FP6) { const int vrc = fp6_validate(a); if (vrc) return vrc; }   // what the path cannot serve: refused first
   SPQ_REQUIRE((a->x || a->stage == SPQ_STAGE_CONTRACTION) && a->w_prep && (a->y || a->out_levels), "spq_linear_lora_fwd: null operand");
   SPQ_REQUIRE(!a->out_levels || (a->path == SPQ_PATH_F16X2 || a->path == SPQ_PATH_F16X3),
               "spq_linear_lora_fwd: the levels-out store exists on the F16X2 / F16X3 operand paths only");
@@ -83,7 +85,7 @@ extern "C" int spq_linear_lora_fwd(const spq_fwd_args* a, spq_stream_t stream) {
               spq_fwd_workspace_bytes(a->M, a->K, a->N, a->r, a->path));
     return SPQ_ERR_WORKSPACE;
   }
-  if (a->path == SPQ_PATH_F16X2 || a->path == SPQ_PATH_U8X2 || a->path == SPQ_PATH_F16X3 || a->path == SPQ_PATH_I8)
+  if (a->path == SPQ_PATH_F16X2 || a->path == SPQ_PATH_U8X2 || a->path == SPQ_PATH_F16X3 || a->path == SPQ_PATH_I8 || a->path == SPQ_PATH_FP6)
     return fwd_f16x2(a, st);
   if (a->path != SPQ_PATH_F32) {
     set_error("spq_linear_lora_fwd: unknown operand path %d", a->path);

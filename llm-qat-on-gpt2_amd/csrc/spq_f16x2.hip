@@ -106,6 +106,9 @@ static F16x2Layout make_layout(int64_t M, int64_t K, int64_t r, int64_t N = 0, i
 }
 
 size_t fwd_f16x2_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t r, int path) {
+  // SPQ_PATH_FP6: the packed level plane ((Mp / 32) * ceil(K/128) * 3072 B, never more than the fp16 plane) sits where the fp16 level
+  // plane sits, at offset 0; the path has no split-K form, so no scratch for one
+  if (path == SPQ_PATH_FP6) return make_layout(M, K, r, 0, 1).total;
   return make_layout(M, K, r, N, path == SPQ_PATH_F16X3 ? 2 : path == SPQ_PATH_I8 ? -1 : 1).total;
 }
 
@@ -281,6 +284,8 @@ __global__ __launch_bounds__(256) void prep_f16x2_kernel(PrepArgs a) {
 //   t[m, j]   = sum_k x[m,k] * FQ(A)[k,j]      fp32-input MFMA, K split over the 4 waves, summed in LDS
 //   thi/tlo   = two fp16 limbs of t * 2^g[m];  rowinv[m] = 2^-g[m]
 // =================================================================================================
+#include "spq_fp6_kernel.h"
+
 struct XPassArgs {
   int* zero_ptr; int zero_n;                // the streaming kernels' block 0 zeroes these ints (the contraction's split-K counters)
   const float* x; const float* sx; const float* zx; const float* aT;   // x [M,K]; aT = FQ(A)^T [r,K] fp32
@@ -298,6 +303,8 @@ struct XPassArgs {
   // (switchable_batchnorm.py:102-109); the pass normalises each row on the fly -- weight * ((x - mean) / sqrt(var + eps)) + bias,
   // bit for bit what spq_layernorm writes -- so the normalised fp32 activation is never stored or re-read.  K <= 1024.
   const float* ln_w; const float* ln_b; float ln_eps;
+  // a8 == 4 (SPQ_PATH_FP6): the levels go out as packed e2m3 codes in MFMA-operand-tile order (spq_fp6_kernel.h), kb6 k blocks of 128
+  unsigned char* a6; int kb6;
 };
 
 // LayerNorm prologue of the panel kernels.  ln_panel_stats: wave w takes rows 4w .. 4w+3 of the workgroup's row block (row in
@@ -748,6 +755,11 @@ __global__ __launch_bounds__(256) void xpass_kernel(XPassArgs a) {
         if (a.limbs) {                                                               // pad columns must come out as zero limbs
           if (k + 0 >= a.K) vv.x = 0.f; if (k + 1 >= a.K) vv.y = 0.f; if (k + 2 >= a.K) vv.z = 0.f; if (k + 3 >= a.K) vv.w = 0.f;
         }
+        if (a.a8 == 4) {                                                             // FP6 form: the row's 16 lanes assemble its two fields
+          fp6_store_chunk(a.a6, a.kb6, m, k0 >> 6, 0, fp6_code4(minmax_level<true>(v.x, s0, 0.f, qlo, qhi), minmax_level<true>(v.y, s1, 0.f, qlo, qhi),
+                                                                minmax_level<true>(v.z, s2, 0.f, qlo, qhi), minmax_level<true>(v.w, s3, 0.f, qlo, qhi)), lane);
+          if (k0 + XK >= a.Kp && ((a.Kp >> 6) & 1)) fp6_store_chunk(a.a6, a.kb6, m, (k0 >> 6) + 1, 0, 0u, lane);   // zero codes up to the 128-deep block's end
+        } else
         store_act4(a, (int64_t)m * a.Kp + k, vv, make_float4(s0, s1, s2, s3), zp4, qlo, qhi, a.limbs ? a.xscale[0] : 1.f);
         if (a.limbs && k + 3 >= a.K) {                                               // FQ(0) need not be 0 (asymmetric / log): force pads
           _Float16* ph = a.qx + (int64_t)m * a.Kp + k; _Float16* pl = a.xl + (int64_t)m * a.Kp + k;
@@ -1002,7 +1014,7 @@ __device__ unsigned long long g_xp_stamps[2048 * 8 * 4];
 // CP + 4 / 4); the chunk's zero points (log: minima) ride in the aux line that carries the LayerNorm weight otherwise, so the
 // LayerNorm prologue and the limb form exclude each other.  The panel kernels spent the log arithmetic (ALU-bound) and the
 // copies one after the other; here the ring keeps two chunks of copies in flight under it.
-template <int ROWS, int A8, bool LN>   // A8 0: fp16 levels; 1: bytes q + 128; 2: int8 q; 3: two fp16 limbs of FQ(x) * 2^G
+template <int ROWS, int A8, bool LN>   // A8 0: fp16 levels; 1: bytes q + 128; 2: int8 q; 3: two fp16 limbs of FQ(x) * 2^G; 4: packed e2m3 levels (FP6)
 __device__ __forceinline__ void xpass_stream_body(const XPassArgs& a, char* xsm, const int block) {
   constexpr int NW = ROWS / 4, SLOT = xs_slot(ROWS), XS_X = ROWS * 256, APW = 16 / NW;   // waves; FQ(A)^T pieces per wave
   float* lnst = reinterpret_cast<float*>(xsm + 3 * SLOT);   // LN only: {mean, den} per row
@@ -1057,13 +1069,13 @@ __device__ __forceinline__ void xpass_stream_body(const XPassArgs& a, char* xsm,
   for (int c = 0; c < nck; ++c) {
     SPQ_XP_STAMP(t0);
     // chunk c's copies are done once only the younger operations remain: {store c-2, CP copies of c+1, store c-1}
-    // (A8 == 3: two limb stores per chunk instead of one level store -> CP + 4 and 4)
+    // (A8 == 3: two limb stores per chunk instead of one level store -> CP + 4 and 4; A8 == 4: the 16-B and 8-B parts of the FP6 fields, two stores too)
     if (c + 1 < nck && c >= 2) {
-      if (A8 == 3) { if (APW == 4) asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
+      if (A8 >= 3) { if (APW == 4) asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
       else if (APW == 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     } else if (c + 1 < nck) {
       if (APW == 4) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    } else if (c >= 2) { if (A8 == 3) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
+    } else if (c >= 2) { if (A8 >= 3) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     SPQ_XP_STAMP(t1);
@@ -1136,7 +1148,10 @@ __device__ __forceinline__ void xpass_stream_body(const XPassArgs& a, char* xsm,
       for (int e = 0; e < 4; ++e) q[e] = minmax_level<true>(v[e], sc[e], 0.f, qlo, qhi);
     }
     if ((!(SPQ_XP_DIAG & 4) && !(SPQ_XP_DIAG & 64)) || a.M == 12345 || ((SPQ_XP_DIAG & 64) && q[0] + q[1] + q[2] + q[3] == 12345.f))
-      store_levels4(a.qx, q_dst + c * 64, q[0], q[1], q[2], q[3], A8);
+    {
+      if (A8 == 4) fp6_store_chunk(a.a6, a.kb6, min(m0 + prow, a.M - 1), c, prow & 15, fp6_code4(q[0], q[1], q[2], q[3]), lane);
+      else store_levels4(a.qx, q_dst + c * 64, q[0], q[1], q[2], q[3], A8);
+    }
     slot = slot == 2 ? 0 : slot + 1;
     if (SPQ_XP_DIAG & 128) {
       asm volatile("s_nop 0" :: "v"(acc[0][0]), "v"(acc[1][0]), "v"(acc[2][0]), "v"(acc[3][0]) : "memory");   // the MFMAs are done
@@ -1150,6 +1165,7 @@ __device__ __forceinline__ void xpass_stream_body(const XPassArgs& a, char* xsm,
     o[0] = st_wait; o[1] = st_bar; o[2] = st_body; o[3] = __builtin_readcyclecounter() - t_begin;
   }
 #endif
+  if (A8 == 4 && (nck & 1)) fp6_store_chunk(a.a6, a.kb6, min(m0 + prow, a.M - 1), nck, prow & 15, 0u, lane);   // zero codes up to the 128-deep block's end
   __syncthreads();                                          // the ring is free for the reduction
   if ((SPQ_XP_DIAG & 16) && a.M != 12345) return;
   xpass16_finish<ROWS>(a, acc, reinterpret_cast<float*>(xsm), m0, tid);
@@ -1680,6 +1696,8 @@ __global__ __launch_bounds__(256, T128_WGS) void gemm_f16x2_t128_kernel(GemmF16A
 #endif
 }
 
+#include "spq_fp6_gemm.h"
+
 // =================================================================================================
 // part2 CPTLinear (cpt_model.py:96-113): the LoRA branch consumes FQ(x) like the base term, so the layer is one contraction
 // against  W_eff = FQ(W) + s FQ(B) FQ(A)^T.  Two small kernels build it; the limb split is the ordinary row kernel.
@@ -1865,10 +1883,28 @@ extern "C" int spq_debug_split_k(int64_t M, int64_t K, int64_t N, int64_t r, int
   return t128_split(nwg, T, nl, (int64_t)T128_WGS * gemm_grid(1 << 30), g_switches.split_k);
 }
 
+// SPQ_PATH_FP6: everything the path cannot serve is refused here, before any launch (spq_linear_lora_fwd calls it first)
+int fp6_validate(const spq_fwd_args* a) {
+  if (!(a->quantize_input && a->qtype == SPQ_MINMAX && a->symmetric && a->bits >= 2 && a->bits <= 4)) {
+    set_error("spq_linear_lora_fwd: SPQ_PATH_FP6 needs a symmetric minmax input quantizer with 2..4 bits "
+              "(got qtype=%d symmetric=%d bits=%d quantize_input=%d)", a->qtype, a->symmetric, a->bits, a->quantize_input);
+    return SPQ_ERR_UNSUPPORTED;
+  }
+  if (a->lora_on_fq_input) { set_error("spq_linear_lora_fwd: SPQ_PATH_FP6 has no lora_on_fq_input form (the LoRA branch reads the raw x)"); return SPQ_ERR_UNSUPPORTED; }
+  if (a->out_levels || a->out_levels_lo) { set_error("spq_linear_lora_fwd: SPQ_PATH_FP6 has no levels-out store"); return SPQ_ERR_UNSUPPORTED; }
+  if (a->epilogue != SPQ_EPILOGUE_NONE && a->epilogue != SPQ_EPILOGUE_GELU) { set_error("spq_linear_lora_fwd: SPQ_PATH_FP6 epilogue %d unknown", a->epilogue); return SPQ_ERR_UNSUPPORTED; }
+  if (a->epilogue == SPQ_EPILOGUE_GELU && (a->N & 3) != 0) { set_error("spq_linear_lora_fwd: the fused GELU epilogue needs N %% 4 == 0 (got N=%lld)", (long long)a->N); return SPQ_ERR_UNSUPPORTED; }
+  if (a->r > 128) { set_error("spq_linear_lora_fwd: SPQ_PATH_FP6 needs LoRA rank <= 128 (got r=%lld)", (long long)a->r); return SPQ_ERR_UNSUPPORTED; }
+  return SPQ_OK;
+}
+
 int fwd_f16x2(const spq_fwd_args* a, hipStream_t st) {
   const bool x3 = a->path == SPQ_PATH_F16X3;
   const int i8nl = i8_limbs_of(a->path);
-  if (i8nl) {
+  const bool fp6 = a->path == SPQ_PATH_FP6;
+  if (fp6) {                                               // (fp6_validate ran in spq_linear_lora_fwd, the only caller)
+    if (a->prepare && a->prepare->path != a->path) { set_error("spq_linear_lora_fwd: prepare args are for another operand path"); return SPQ_ERR_INVALID; }
+  } else if (i8nl) {
     if (!(a->quantize_input && a->qtype == SPQ_MINMAX && a->symmetric && a->bits >= 2 && a->bits <= 8)) {
       set_error("spq_linear_lora_fwd: the int8 operand paths need a symmetric minmax input quantizer with 2..8 bits "
                 "(got qtype=%d symmetric=%d bits=%d quantize_input=%d)", a->qtype, a->symmetric, a->bits, a->quantize_input);
@@ -1891,7 +1927,7 @@ int fwd_f16x2(const spq_fwd_args* a, hipStream_t st) {
     return SPQ_ERR_UNSUPPORTED;
   }
   SPQ_REQUIRE(a->w_rowscale, "spq_linear_lora_fwd: w_rowscale missing for SPQ_PATH_F16X2");
-  const F16x2Layout L = make_layout(a->M, a->K, a->r, a->N, x3 ? 2 : i8nl ? -1 : 1);
+  const F16x2Layout L = make_layout(a->M, a->K, a->r, fp6 ? 0 : a->N, x3 ? 2 : i8nl ? -1 : 1);
   const PrepLayout P = make_prep_layout(a->N, a->K, a->r);
   char* ws = (char*)a->workspace;
   const char* wp = (const char*)a->w_prep;
@@ -1920,7 +1956,8 @@ int fwd_f16x2(const spq_fwd_args* a, hipStream_t st) {
     set_error("spq_linear_lora_fwd: a_limb_scale (LoRA-down on the f16 pipe, tools/variants/xpass_panel16.h) is no longer in the library; pass null");
     return SPQ_ERR_UNSUPPORTED;
   }
-  x.a8 = i8nl ? 2 : 0;
+  x.a8 = fp6 ? 4 : i8nl ? 2 : 0;
+  x.a6 = (unsigned char*)(ws + L.off_qx); x.kb6 = (int)((a->K + 127) / 128);
   const unsigned xgrid = (unsigned)((a->M + XR - 1) / XR);
   const bool panel_ok = (a->K % 64 == 0) && L.Rp <= 64 && aligned16(a->x) && (a->r == 0 || aligned16(a->a_prep)) && aligned16(x.sx) &&
                         aligned16(x.zx);
@@ -1935,7 +1972,7 @@ int fwd_f16x2(const spq_fwd_args* a, hipStream_t st) {
   // split-K of the contraction (f16 limb kernels): decided here because the activation launch zeroes its counters
   int sk = 1;
   const int64_t sk_nwg = (L.Mp / 128) * (P.Np / GN);
-  if (!i8nl && do_gemm && a->epilogue == SPQ_EPILOGUE_NONE && !a->out_levels && (a->N & 3) == 0) {
+  if (!i8nl && !fp6 && do_gemm && a->epilogue == SPQ_EPILOGUE_NONE && !a->out_levels && (a->N & 3) == 0) {
     const int nl = lora_up ? (int)(L.Rp / GK) * 2 : 0;
     const int T = nl + (x3 ? 2 : 1) * (int)(L.Kp / GK);
     sk = t128_split(sk_nwg, T, nl, (int64_t)T128_WGS * gemm_grid(1 << 30), sw.split_k);
@@ -1951,7 +1988,7 @@ int fwd_f16x2(const spq_fwd_args* a, hipStream_t st) {
     int prc = prepare_fill(a->prepare, pa, at_blocks, wave_ok);
     if (prc) return prc;
     if (a->prepare->N != a->N || a->prepare->K != a->K || a->prepare->r < a->r) { set_error("spq_linear_lora_fwd: prepare args describe another layer"); return SPQ_ERR_INVALID; }
-    if (sw.prep_role && stream_ok && !a->ln_weight && wave_ok && a->K <= 1024) {
+    if (sw.prep_role && !fp6 && stream_ok && !a->ln_weight && wave_ok && a->K <= 1024) {
       role_prep = true;
       if (at_blocks) {
         fq_transpose_kernel<<<(unsigned)at_blocks, 256, 0, st>>>(pa);
@@ -1967,15 +2004,21 @@ int fwd_f16x2(const spq_fwd_args* a, hipStream_t st) {
     return SPQ_ERR_INVALID;
   }
   if (a->ln_weight && do_xpass) {
-    // the LayerNorm prologue lives in the panel kernels (fp32-MFMA LoRA-down), rows of at most 1024 elements
-    if (!a->ln_bias || !panel_ok || a->K > 1024 || !aligned16(a->ln_weight) || !aligned16(a->ln_bias)) {
+    // the LayerNorm prologue lives in the panel and streaming kernels (fp32-MFMA LoRA-down), rows of at most 1024 elements; the FP6
+    // store form exists in the streaming kernel only
+    if (fp6 && panel_ok && !stream_ok) {
+      set_error("spq_linear_lora_fwd: SPQ_PATH_FP6 + LayerNorm prologue needs the streaming activation kernel (rank > 0, SPQ_XPASS_STREAM not 0); "
+                "run spq_layernorm first");
+      return SPQ_ERR_UNSUPPORTED;
+    }
+    if (!a->ln_bias || !panel_ok || (fp6 && !stream_ok) || a->K > 1024 || !aligned16(a->ln_weight) || !aligned16(a->ln_bias)) {
       set_error("spq_linear_lora_fwd: the LayerNorm prologue needs K %% 64 == 0, K <= 1024, rank <= 64 and 16-byte aligned operands");
       return SPQ_ERR_UNSUPPORTED;
     }
   }
   if (!do_xpass) {
     // the activation pass of this call ran earlier (same arguments, same workspace)
-  } else if (panel_ok) {
+  } else if (panel_ok && (!fp6 || stream_ok)) {           // (FP6 store form: the streaming kernel, or the generic kernel below)
     if (AttrOnce once(0); once.first) {
       hipError_t e = hipFuncSetAttribute((const void*)xpass_panel_kernel<XP_CHUNKS>, hipFuncAttributeMaxDynamicSharedMemorySize, XP_LDS);
       if (e != hipSuccess) { set_error("hipFuncSetAttribute(xpass LDS %d B): %s", XP_LDS, hipGetErrorString(e)); return SPQ_ERR_LAUNCH; }
@@ -1988,6 +2031,7 @@ int fwd_f16x2(const spq_fwd_args* a, hipStream_t st) {
         SPQ_XS_ATTR(16, 0, false); SPQ_XS_ATTR(16, 2, false); SPQ_XS_ATTR(16, 0, true); SPQ_XS_ATTR(16, 2, true);
         SPQ_XS_ATTR(32, 0, false); SPQ_XS_ATTR(32, 2, false); SPQ_XS_ATTR(32, 0, true); SPQ_XS_ATTR(32, 2, true);
         SPQ_XS_ATTR(16, 3, false); SPQ_XS_ATTR(32, 3, false); SPQ_XS_ATTR(16, 3, true); SPQ_XS_ATTR(32, 3, true);
+        SPQ_XS_ATTR(16, 4, false); SPQ_XS_ATTR(32, 4, false); SPQ_XS_ATTR(16, 4, true); SPQ_XS_ATTR(32, 4, true);
 #undef SPQ_XS_ATTR
       }
       // 32-row workgroups halve the FQ(A)^T traffic through L2; taken once they still cover every CU
@@ -2011,7 +2055,8 @@ int fwd_f16x2(const spq_fwd_args* a, hipStream_t st) {
 #define SPQ_XS_LAUNCH(R, A8, LN) xpass_stream_kernel<R, A8, LN><<<(unsigned)((a->M + R - 1) / R), R * 16, xs_lds(R), st>>>(x)
 #define SPQ_XS_PICK(R) do { if (ln) { if (x.a8 == 0) SPQ_XS_LAUNCH(R, 0, true); else SPQ_XS_LAUNCH(R, 2, true); } \
                             else { if (x.a8 == 0) SPQ_XS_LAUNCH(R, 0, false); else SPQ_XS_LAUNCH(R, 2, false); } } while (0)
-        if (x.limbs && ln) { if (r32) SPQ_XS_LAUNCH(32, 3, true); else SPQ_XS_LAUNCH(16, 3, true); }
+        if (fp6) { if (ln) { if (r32) SPQ_XS_LAUNCH(32, 4, true); else SPQ_XS_LAUNCH(16, 4, true); } else { if (r32) SPQ_XS_LAUNCH(32, 4, false); else SPQ_XS_LAUNCH(16, 4, false); } }
+        else if (x.limbs && ln) { if (r32) SPQ_XS_LAUNCH(32, 3, true); else SPQ_XS_LAUNCH(16, 3, true); }
         else if (x.limbs) { if (r32) SPQ_XS_LAUNCH(32, 3, false); else SPQ_XS_LAUNCH(16, 3, false); }
         else if (r32) SPQ_XS_PICK(32); else SPQ_XS_PICK(16);
 #undef SPQ_XS_PICK
@@ -2024,6 +2069,30 @@ int fwd_f16x2(const spq_fwd_args* a, hipStream_t st) {
   int rc = check_launch("spq_linear_lora_fwd(xpass)");
   if (rc || !do_gemm) return rc;
 
+  if (fp6) {
+    const PrepLayoutFp6 P6 = make_prep_layout_fp6(a->N, a->K, a->r);
+    GemmFp6Args q;
+    q.A6 = x.a6; q.W6 = (const unsigned char*)wp; q.plane_stride = (int64_t)P6.plane;
+    q.rowscale = a->w_rowscale; q.bfac = (const float*)(wp + P6.off_bfac); q.bias = a->bias; q.y = a->y;
+    q.M = (int)a->M; q.N = (int)a->N; q.KB = (int)P6.KB; q.tiles_m = (int)(L.Mp / 128); q.tiles_n = (int)(P6.Np / 128);
+    q.thi = x.thi; q.tlo = x.tlo; q.Bhi = (const _Float16*)(wp + P6.off_bhi); q.Blo = (const _Float16*)(wp + P6.off_blo);
+    q.rowinv = x.rowinv; q.Rp = lora_up ? (int)L.Rp : 0;
+    if (AttrOnce once(9); once.first) {
+      hipError_t e = hipFuncSetAttribute((const void*)gemm_fp6_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, F6_LDS);
+      if (e != hipSuccess) { set_error("hipFuncSetAttribute(LDS %d B): %s", F6_LDS, hipGetErrorString(e)); return SPQ_ERR_LAUNCH; }
+      (void)hipFuncSetAttribute((const void*)gemm_fp6_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, F6_LDS);
+      (void)hipFuncSetAttribute((const void*)gemm_fp6_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, F6_LDS);
+    }
+    const int ntiles = q.tiles_m * q.tiles_n;
+    const unsigned cus3 = 3 * gemm_grid(1 << 30);
+    const unsigned grid6 = (unsigned)ntiles < cus3 ? (unsigned)ntiles : cus3;
+    if (a->ev_gemm_begin) (void)hipEventRecord((hipEvent_t)a->ev_gemm_begin, st);
+    if ((a->N & 3) != 0) gemm_fp6_kernel<0, true><<<grid6, 256, F6_LDS, st>>>(q);           // (fp6_validate: no GELU with a ragged N)
+    else if (a->epilogue == SPQ_EPILOGUE_GELU) gemm_fp6_kernel<1, false><<<grid6, 256, F6_LDS, st>>>(q);
+    else gemm_fp6_kernel<0, false><<<grid6, 256, F6_LDS, st>>>(q);
+    if (a->ev_gemm_end) (void)hipEventRecord((hipEvent_t)a->ev_gemm_end, st);
+    return check_launch("spq_linear_lora_fwd(gemm_fp6)");
+  }
   if (i8nl) {
     const PrepLayoutI8 P8 = make_prep_layout_i8(a->N, a->K, a->r, i8nl);
     GemmI8Args q;
@@ -2139,6 +2208,7 @@ extern "C" size_t spq_prep_f16x2_bytes(int64_t N, int64_t K, int64_t r) {
 extern "C" size_t spq_prep_bytes(int64_t N, int64_t K, int64_t r, int path) {
   if (N <= 0 || K <= 0 || r < 0) return 0;
   const int nl = i8_limbs_of(path);
+  if (path == SPQ_PATH_FP6) return make_prep_layout_fp6(N, K, r).total;
   return nl ? make_prep_layout_i8(N, K, r, nl).total : make_prep_layout(N, K, r).total;
 }
 
@@ -2154,11 +2224,13 @@ int prepare_fill(const spq_prepare_args* q, PrepArgs& a, int& at_blocks, bool& w
   const int64_t N = q->N, K = q->K, r = q->r;
   if (!f16x2_shape_ok(1, K, N, r)) { set_error("spq_prepare_f16x2: needs LoRA rank <= 128 (got r=%lld)", (long long)r); return SPQ_ERR_UNSUPPORTED; }
   const int nl = i8_limbs_of(q->path);
-  SPQ_REQUIRE(nl || q->path == 0 || q->path == SPQ_PATH_F16X2 || q->path == SPQ_PATH_U8X2 || q->path == SPQ_PATH_F16X3,
+  const bool fp6 = q->path == SPQ_PATH_FP6;
+  SPQ_REQUIRE(nl || fp6 || q->path == 0 || q->path == SPQ_PATH_F16X2 || q->path == SPQ_PATH_U8X2 || q->path == SPQ_PATH_F16X3,
               "spq_prepare_f16x2: unknown operand path %d", q->path);
   const PrepLayout P = make_prep_layout(N, K, r);
   const PrepLayoutI8 P8 = make_prep_layout_i8(N, K, r, nl);
-  const size_t need = nl ? P8.total : P.total;
+  const PrepLayoutFp6 P6 = make_prep_layout_fp6(N, K, r);
+  const size_t need = fp6 ? P6.total : nl ? P8.total : P.total;
   if (q->w_prep_bytes < need || !aligned16(q->w_prep)) { set_error("spq_prepare_f16x2: buffer too small (%zu < %zu)", q->w_prep_bytes, need); return SPQ_ERR_WORKSPACE; }
   char* wp = (char*)q->w_prep;
   a.W = q->W; a.sw = q->sw; a.zw = q->zw; a.B = r > 0 ? q->B : nullptr; a.sb = q->sb; a.zb = q->zb; a.sx = q->sx;
@@ -2172,6 +2244,10 @@ int prepare_fill(const spq_prepare_args* q, PrepArgs& a, int& at_blocks, bool& w
     a.W8 = (signed char*)wp; a.plane_stride = (int64_t)P8.plane;
     a.Bhi = P8.Rp ? (_Float16*)(wp + P8.off_bhi) : nullptr; a.Blo = P8.Rp ? (_Float16*)(wp + P8.off_blo) : nullptr;
     a.bscale = (float*)(wp + P8.off_bscale);
+  } else if (fp6) {                                       // digit planes at offset 0 (prep_fp6_kernel), LoRA-B limbs behind them
+    a.Whi = a.Wlo = nullptr;
+    a.Bhi = P6.Rp ? (_Float16*)(wp + P6.off_bhi) : nullptr; a.Blo = P6.Rp ? (_Float16*)(wp + P6.off_blo) : nullptr;
+    a.bscale = (float*)(wp + P6.off_bfac);
   } else {
     a.Whi = (_Float16*)(wp + P.off_whi); a.Wlo = (_Float16*)(wp + P.off_wlo);
     a.Bhi = P.Rp ? (_Float16*)(wp + P.off_bhi) : nullptr; a.Blo = P.Rp ? (_Float16*)(wp + P.off_blo) : nullptr;
@@ -2186,6 +2262,7 @@ int prepare_fill(const spq_prepare_args* q, PrepArgs& a, int& at_blocks, bool& w
   at_blocks = (r > 0 && q->A) ? (int)(((r + 31) / 32) * ((K + 31) / 32)) : 0;   // A == NULL: FQ(A)^T is made elsewhere
   wave_ok = (K % 4 == 0) && K <= 4 * 64 * PREP_MAXI && aligned16(q->W) && (!q->x_per_channel || aligned16(q->sx)) && r <= 128;
   a.row_blocks = wave_ok ? (int)(P.Np / 4) : (int)P.Np;
+  if (fp6) { wave_ok = false; a.row_blocks = (int)(P6.Np / 32); }
   if (nl && !wave_ok) {
     set_error("spq_prepare_f16x2: the int8 operand paths need K %% 4 == 0, K <= %d and 16-byte aligned W / sx", 4 * 64 * PREP_MAXI);
     return SPQ_ERR_UNSUPPORTED;
@@ -2202,6 +2279,13 @@ extern "C" int spq_prepare_f16x2_args(const spq_prepare_args* q, spq_stream_t st
   if (rc) return rc;
   const unsigned grid = (unsigned)(a.row_blocks + at_blocks);
   const bool short_rows = q->K <= 4 * 64 * 4;
+  if (q->path == SPQ_PATH_FP6) {
+    const PrepLayoutFp6 P6 = make_prep_layout_fp6(q->N, q->K, q->r);
+    PrepFp6Args f;
+    f.planes = (unsigned char*)q->w_prep; f.plane_stride = (int64_t)P6.plane; f.KB = (int)P6.KB; f.bfac = a.bscale;
+    prep_fp6_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a, f);
+    return check_launch("spq_prepare_f16x2(fp6)");
+  }
   if (a.nl == 1 && short_rows) prep_wave_kernel<1, 4><<<grid, 256, 0, (hipStream_t)stream>>>(a, at_blocks);
   else if (a.nl == 1) prep_wave_kernel<1><<<grid, 256, 0, (hipStream_t)stream>>>(a, at_blocks);
   else if (wave_ok && short_rows) prep_wave_kernel<0, 4><<<grid, 256, 0, (hipStream_t)stream>>>(a, at_blocks);

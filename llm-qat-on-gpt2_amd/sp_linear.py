@@ -298,7 +298,10 @@ class SPLinearWithLoRA(nn.Module):
         if K % 64 != 0 or K > 1024 or tuple(norm.normalized_shape) != (K,) or x.shape[-1] != K:
             return False
         use_lora = (not self.calibration_mode) and lora.enabled and lora.scaling != 0
-        return self._choose_path(qx, qw, lora, use_lora, 1) in (_lib.PATH_F16X2, _lib.PATH_F16X3, _lib.PATH_I8)
+        path = self._choose_path(qx, qw, lora, use_lora, 1)
+        if path == _lib.PATH_FP6:      # its LayerNorm prologue lives in the streaming activation kernel only
+            return os.environ.get('SPQ_XPASS_STREAM', '1')[:1] != '0'
+        return path in (_lib.PATH_F16X2, _lib.PATH_F16X3, _lib.PATH_I8)
 
     def _forward(self, x, activation=None):
         self._activation_fused = False
@@ -397,7 +400,7 @@ class SPLinearWithLoRA(nn.Module):
             nw, nb = norm.weights[str(norm.current_precision)], norm.biases[str(norm.current_precision)]
             a.ln_weight, a.ln_bias, a.ln_eps = nw.data_ptr(), nb.data_ptr(), float(norm.eps)
             self._norm_fused = True
-        if activation == 'gelu' and (prep.path == _lib.PATH_I8 or (prep.path in (_lib.PATH_F16X2, _lib.PATH_F16X3) and N % 4 == 0)):
+        if activation == 'gelu' and (prep.path == _lib.PATH_I8 or (prep.path in (_lib.PATH_F16X2, _lib.PATH_F16X3, _lib.PATH_FP6) and N % 4 == 0)):
             a.epilogue = _lib.EPILOGUE_GELU
             self._activation_fused = True
         with _lib.on_device(x.device):
@@ -436,11 +439,19 @@ class SPLinearWithLoRA(nn.Module):
         i8_ok = bool(f16_ok and qx.num_bits <= 8 and self.in_features % 4 == 0 and self.in_features <= 4096
                      and qw is not None and qw.quantizer_type == 'minmax' and qw.symmetric and 2 <= qw.num_bits <= 8
                      and qx.scale.numel() == 1 and use_lora and lora is not None and lora.rank > 0)
+        # FP6 matrix cores (SPQ_PATH_FP6): levels of <= 4 bits are exact e2m3 numbers, the weight goes in as five radix-32 digit
+        # planes (csrc/spq_fp6_kernel.h).  e2m3 has no NaN either, so the int8 path's rule applies: only with a LoRA-up term running
+        # does a NaN activation still reach its output row (through the fp32 LoRA-down product).
+        fp6_ok = bool(f16_ok and qx.num_bits <= 4 and use_lora and lora is not None and lora.rank > 0)
+        if self.operand_path == _lib.PATH_FP6:
+            return _lib.PATH_FP6 if fp6_ok else (_lib.PATH_F16X2 if f16_ok else (_lib.PATH_F16X3 if x3_ok else _lib.PATH_F32))
         if self.operand_path == _lib.PATH_I8:
             return _lib.PATH_I8 if i8_ok else (_lib.PATH_F16X2 if f16_ok else (_lib.PATH_F16X3 if x3_ok else _lib.PATH_F32))
         if self.operand_path == _lib.PATH_AUTO:
             if _AUTO_I8 and i8_ok:
                 return _lib.PATH_I8
+            if _AUTO_FP6 and fp6_ok:
+                return _lib.PATH_FP6
             return _lib.PATH_F16X2 if f16_ok else (_lib.PATH_F16X3 if x3_ok else _lib.PATH_F32)
         if self.operand_path == _lib.PATH_F16X3:
             return _lib.PATH_F16X3 if (x3_ok or f16_ok) else _lib.PATH_F32
@@ -554,9 +565,11 @@ class SPLinearWithLoRA(nn.Module):
         prep.b = prep.w      # LoRA-B limbs live inside the same buffer
 
 
-_LIMB_PATHS = (_lib.PATH_F16X2, _lib.PATH_F16X3, _lib.PATH_I8)
+_LIMB_PATHS = (_lib.PATH_F16X2, _lib.PATH_F16X3, _lib.PATH_I8, _lib.PATH_FP6)
 # SPQ_AUTO_I8=0: PATH_AUTO never picks the int8 operand path (then: F16X2 wherever it would be valid)
 _AUTO_I8 = os.environ.get('SPQ_AUTO_I8', '1')[:1] != '0'
+# SPQ_AUTO_FP6=1: PATH_AUTO picks the FP6 operand path wherever it is valid and int8 is not chosen (off by default)
+_AUTO_FP6 = os.environ.get('SPQ_AUTO_FP6', '0')[:1] == '1'
 _ones_cache = {}
 
 

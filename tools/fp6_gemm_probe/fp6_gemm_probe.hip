@@ -1,4 +1,4 @@
-// Proof of concept for DESIGN.md section 6 "another operand format" (NOT part of the library): the base contraction of the headline
+// Comparison harness for the FP6 operand path (the library ships gemm_fp6_h3_kernel's form as gemm_fp6_kernel): the base contraction of the headline
 // layer with FP6 (e2m3) operands on v_mfma_scale_f32_16x16x128_f8f6f4 --
 //   activation levels q in [-7, 7]: exact in e2m3;
 //   W' = FQ(W)[n,k] sx[k], scaled per row to a 25-bit integer w = round(W' 2^E[n]), as FIVE balanced radix-32 digits d_i, |d_i| <= 16,

@@ -1,5 +1,5 @@
-// Building blocks for the FP6 operand format of DESIGN.md section 6 (round-4 plan; NOT part of the library): the two packing kernels the
-// production path will need, checked bit for bit against the host packing that tools/fp6_gemm_probe/fp6_gemm_probe.hip feeds its kernels.
+// Building blocks for the FP6 operand format (the library's own packing lives in csrc/spq_fp6_kernel.h and rounds the weight
+// once, in fp64): two stand-alone packing kernels, checked bit for bit against the host packing that tools/fp6_gemm_probe/fp6_gemm_probe.hip feeds its kernels.
 //   fp6_levels_kernel : activation levels q = clamp(rint(x / sx[k]), -7, 7) -> e2m3 codes, packed in MFMA-operand-tile order
 //   fp6_digits_kernel : W'[n,k] (fp32) -> per-row power of two 2^E[n], w = round(W' 2^E) as a 25-bit integer, five balanced radix-32 digits
 //                       (|d| <= 16) as e2m3 codes of d / 8, one packed plane per digit; rowscale[n] = 2^-E[n]

@@ -6,12 +6,12 @@ from llm_qat_on_gpt2_amd import synthetic as O          # seeded input generator
 dev = 'cuda:0'
 L = pkg._lib
 CASES = [  # M, K, N, r, bits, qtype, paths
-    (8192, 768, 3072, 64, 4, 'minmax', ['f16x2', 'f16x3', 'f32']),
+    (8192, 768, 3072, 64, 4, 'minmax', ['fp6', 'f16x2', 'f16x3', 'f32']),
     (8192, 1024, 4096, 64, 6, 'log', ['f16x3', 'f32']),
     (8192, 4096, 1024, 64, 6, 'log', ['f16x3', 'f32']),
     (8192, 768, 3072, 64, 16, 'minmax', ['f16x3', 'f32']),
 ]
-P = {'f16x2': L.PATH_F16X2, 'f16x3': L.PATH_F16X3, 'f32': L.PATH_F32}
+P = {'fp6': L.PATH_FP6, 'f16x2': L.PATH_F16X2, 'f16x3': L.PATH_F16X3, 'f32': L.PATH_F32}
 for M, K, N, r, bits, qt, paths in CASES:
     W, bias, A, B, x0, x1 = O.make_workload(M, K, N, r, seed=0, batch=8)
     layer = pkg.SPLinearWithLoRA(K, N, [bits, 32], {bits: r, 32: 0}, {bits: 64, 32: 0}, {bits: qt, 32: None})
