@@ -28,7 +28,7 @@ int launch_gemm_f32_nt(const float* A, int64_t lda, const float* B, int64_t ldb,
                        int64_t lda2, const float* B2, int64_t ldb2, int64_t K2, float alpha2,
                        const float* bias, float* C, int64_t ldc, int64_t M, int64_t N, hipStream_t st);
 int fwd_f16x2(const spq_fwd_args* a, hipStream_t st);
-int fp6_validate(const spq_fwd_args* a);
+int fwd_check_common(const spq_fwd_args* a);
 size_t fwd_f16x2_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t r, int path);
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -67,11 +67,8 @@ extern "C" size_t spq_fwd_workspace_bytes(int64_t M, int64_t K, int64_t N, int64
   return align_up((size_t)M * K * sizeof(float), 256) + align_up((size_t)M * (size_t)r * sizeof(float), 256) + 256;
 }
 
-extern "C" int spq_linear_lora_fwd(const spq_fwd_args* a, spq_stream_t stream) {
-  SPQ_REQUIRE(a, "spq_linear_lora_fwd: null args");
-  SPQ_REQUIRE(a->M > 0 && a->K > 0 && a->N > 0 && a->r >= 0, "spq_linear_lora_fwd: bad shape M=%lld K=%lld N=%lld r=%lld",
-              (long long)a->M, (long long)a->K, (long long)a->N, (long long)a->r);
-  if (a->path == SPQ_PATH_FP6) { const int vrc = fp6_validate(a); if (vrc) return vrc; }   // what the path cannot serve: refused first
+// the checks of spq_linear_lora_fwd that every operand path shares (the limb / int8 / FP6 paths: from fwd_validate, spq_f16x2.hip)
+int spq::fwd_check_common(const spq_fwd_args* a) {
   SPQ_REQUIRE((a->x || a->stage == SPQ_STAGE_CONTRACTION) && a->w_prep && (a->y || a->out_levels), "spq_linear_lora_fwd: null operand");
   SPQ_REQUIRE(!a->out_levels || (a->path == SPQ_PATH_F16X2 || a->path == SPQ_PATH_F16X3),
               "spq_linear_lora_fwd: the levels-out store exists on the F16X2 / F16X3 operand paths only");
@@ -79,14 +76,23 @@ extern "C" int spq_linear_lora_fwd(const spq_fwd_args* a, spq_stream_t stream) {
   SPQ_REQUIRE(!a->quantize_input || (a->bits >= 1 && a->bits <= 24), "spq_linear_lora_fwd: bits %d outside [1,24]", a->bits);
   SPQ_REQUIRE(a->r == 0 || (a->a_prep && (a->b_prep || a->t_out)), "spq_linear_lora_fwd: LoRA operands missing");
   SPQ_REQUIRE(a->workspace && aligned16(a->workspace), "spq_linear_lora_fwd: workspace missing or misaligned");
-  hipStream_t st = (hipStream_t)stream;
-  if (a->workspace_bytes < spq_fwd_workspace_bytes(a->M, a->K, a->N, a->r, a->path)) {
-    set_error("spq_linear_lora_fwd: workspace %zu B < required %zu B", a->workspace_bytes,
-              spq_fwd_workspace_bytes(a->M, a->K, a->N, a->r, a->path));
+  const size_t need = spq_fwd_workspace_bytes(a->M, a->K, a->N, a->r, a->path);
+  if (a->workspace_bytes < need) {
+    set_error("spq_linear_lora_fwd: workspace %zu B < required %zu B", a->workspace_bytes, need);
     return SPQ_ERR_WORKSPACE;
   }
+  return SPQ_OK;
+}
+
+extern "C" int spq_linear_lora_fwd(const spq_fwd_args* a, spq_stream_t stream) {
+  SPQ_REQUIRE(a, "spq_linear_lora_fwd: null args");
+  SPQ_REQUIRE(a->M > 0 && a->K > 0 && a->N > 0 && a->r >= 0, "spq_linear_lora_fwd: bad shape M=%lld K=%lld N=%lld r=%lld",
+              (long long)a->M, (long long)a->K, (long long)a->N, (long long)a->r);
+  hipStream_t st = (hipStream_t)stream;
   if (a->path == SPQ_PATH_F16X2 || a->path == SPQ_PATH_U8X2 || a->path == SPQ_PATH_F16X3 || a->path == SPQ_PATH_I8 || a->path == SPQ_PATH_FP6)
-    return fwd_f16x2(a, st);
+    return fwd_f16x2(a, st);                               // validate -> plan -> launch, spq_f16x2.hip
+  int rc = fwd_check_common(a);
+  if (rc) return rc;
   if (a->path != SPQ_PATH_F32) {
     set_error("spq_linear_lora_fwd: unknown operand path %d", a->path);
     return SPQ_ERR_UNSUPPORTED;
@@ -98,7 +104,6 @@ extern "C" int spq_linear_lora_fwd(const spq_fwd_args* a, spq_stream_t stream) {
   float* xq = (float*)ws;
   float* t = a->t_out ? a->t_out : (float*)(ws + align_up((size_t)a->M * a->K * sizeof(float), 256));
   const bool lora_up = a->r > 0 && a->b_prep != nullptr;
-  int rc;
   const float* act = a->x;
   if (a->quantize_input) {  // lora.py:141
     rc = spq_fakequant(a->x, a->M, a->K, 1, a->sx, a->zx, a->x_per_channel, a->bits, a->qtype, a->symmetric, xq,

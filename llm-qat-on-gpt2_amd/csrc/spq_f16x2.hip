@@ -73,20 +73,7 @@ static int t128_split(int64_t nwg, int T, int nl, int64_t slots, int forced) {
   return best;
 }
 unsigned gemm_grid(int ntiles);
-int split_k_switch();
-// units (workgroups) of the split-K form to reserve scratch for: the largest split the forward could take for this shape under the
-// current SPQ_SPLIT_K, over both activation-limb counts and with / without LoRA stages (the workspace is sized before those are known)
-static int64_t sk_reserve_units(int64_t M, int64_t K, int64_t N, int64_t r, int al_only) {   // al_only: 1 / 2 activation limbs, 0 = either
-  const int64_t nwg = (pad_to(M, 256) / 128) * (pad_to(N, 128) / 128);
-  const int64_t slots = 3 * (int64_t)gemm_grid(1 << 30);
-  const int forced = split_k_switch();
-  if (al_only < 0) return 0;                               // (the int8 kernels have no split-K form)
-  const int kb = (int)(pad_to(K, 64) / 64), nlr = r > 0 ? (int)(pad_to(r, 64) / 64) * 2 : 0;
-  int S = 1;
-  for (int al = (al_only ? al_only : 1); al <= (al_only ? al_only : 2); ++al)
-    for (int nl : {0, nlr}) S = std::max(S, t128_split(nwg, nl + al * kb, nl, slots, forced));
-  return S > 1 ? nwg * S : 0;
-}
+static int64_t sk_reserve_units(int64_t M, int64_t K, int64_t N, int64_t r, int al_only);   // host side, next to the forward's plan
 
 static F16x2Layout make_layout(int64_t M, int64_t K, int64_t r, int64_t N = 0, int al = 0) {
   F16x2Layout L;
@@ -1848,8 +1835,6 @@ struct AttrOnce {
   }
 };
 
-int prepare_fill(const spq_prepare_args* q, PrepArgs& a, int& at_blocks, bool& wave_ok);
-
 #if SPQ_XP_DIAG & 128
 extern "C" int spq_debug_xp_stamps(unsigned long long* host_out, int n) {
   return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_xp_stamps), sizeof(unsigned long long) * n, 0, hipMemcpyDeviceToHost);
@@ -1873,327 +1858,376 @@ static Switches read_switches() {
 }
 static Switches g_switches = read_switches();
 extern "C" int spq_debug_reload_switches(void) { g_switches = read_switches(); return SPQ_OK; }
-int split_k_switch() { return g_switches.split_k; }
+
+// The split-K factor of the f16-limb contraction for one shape: the ONE copy of its tile / stage arithmetic (128 x 128 tiles of
+// pad(M, 256) x pad(N, 128); 64-deep stages: al per k block + two per 64 LoRA-up columns).  The forward's plan, the workspace
+// reserve and spq_debug_split_k (tests/test_split_k_host.py) all come here.  r_up = 0: no LoRA-up stages.
+static int64_t t128_tiles(int64_t M, int64_t N) { return (pad_to(M, GM) / 128) * (pad_to(N, GN) / 128); }
+static int t128_split_of(int64_t M, int64_t K, int64_t N, int64_t r_up, int al, int cus, int forced) {
+  const int nl = r_up > 0 ? (int)(pad_to(r_up, GK) / GK) * 2 : 0;
+  return t128_split(t128_tiles(M, N), nl + al * (int)(pad_to(K, GK) / GK), nl, (int64_t)T128_WGS * cus, forced);
+}
+// units (workgroups) of the split-K form to reserve scratch for: the largest split the forward could take for this shape under the
+// current SPQ_SPLIT_K, over both activation-limb counts and with / without LoRA stages (the workspace is sized before those are known)
+static int64_t sk_reserve_units(int64_t M, int64_t K, int64_t N, int64_t r, int al_only) {   // al_only: 1 / 2 activation limbs, 0 = either
+  if (al_only < 0) return 0;                               // (the int8 kernels have no split-K form)
+  const int cus = (int)gemm_grid(1 << 30);
+  int S = 1;
+  for (int al = (al_only ? al_only : 1); al <= (al_only ? al_only : 2); ++al)
+    for (int64_t ru : {(int64_t)0, r}) S = std::max(S, t128_split_of(M, K, N, ru, al, cus, g_switches.split_k));
+  return S > 1 ? t128_tiles(M, N) * S : 0;
+}
 // host logic, no launch: how many units per tile the forward would use for this shape under the current switches (CPU-tested)
 extern "C" int spq_debug_split_k(int64_t M, int64_t K, int64_t N, int64_t r, int path) {
   if (M <= 0 || K <= 0 || N <= 0 || r < 0 || (path != SPQ_PATH_F16X2 && path != SPQ_PATH_F16X3) || (N & 3) != 0) return 1;
-  const int64_t nwg = (pad_to(M, 256) / 128) * (pad_to(N, 128) / 128);
-  const int nl = r > 0 ? (int)(pad_to(r, 64) / 64) * 2 : 0;
-  const int T = nl + (path == SPQ_PATH_F16X3 ? 2 : 1) * (int)(pad_to(K, 64) / 64);
-  return t128_split(nwg, T, nl, (int64_t)T128_WGS * gemm_grid(1 << 30), g_switches.split_k);
+  return t128_split_of(M, K, N, r, path == SPQ_PATH_F16X3 ? 2 : 1, (int)gemm_grid(1 << 30), g_switches.split_k);
 }
 
-// SPQ_PATH_FP6: everything the path cannot serve is refused here, before any launch (spq_linear_lora_fwd calls it first)
-int fp6_validate(const spq_fwd_args* a) {
-  if (!(a->quantize_input && a->qtype == SPQ_MINMAX && a->symmetric && a->bits >= 2 && a->bits <= 4)) {
-    set_error("spq_linear_lora_fwd: SPQ_PATH_FP6 needs a symmetric minmax input quantizer with 2..4 bits "
-              "(got qtype=%d symmetric=%d bits=%d quantize_input=%d)", a->qtype, a->symmetric, a->bits, a->quantize_input);
-    return SPQ_ERR_UNSUPPORTED;
+// ---- kernel families -------------------------------------------------------------------------------------------------
+// One table per family: a row pairs the selector key with the instantiation it selects and that instantiation's dynamic LDS.
+// The launch looks its row up here, and the first use of a family on a device raises the LDS limit of ALL its rows (under the
+// per-device lock), so a variant first met during stream capture needs no hipFuncSetAttribute (tests/test_gpu_graph.py).  The
+// activation families are raised as a chain (launch_xpass): a layer's first forward runs streaming + preparation, its later ones
+// plain streaming, and those may already be inside a capture.  A selector without a row is refused by fwd_validate.
+enum { X_NONE, X_GENERIC, X_PANEL, X_STREAM, X_STREAM_PREP };            // activation launch (X_NONE: SPQ_STAGE_CONTRACTION)
+enum { G_NONE, G_FP6, G_I8, G_T128 };                                    // contraction launch (G_NONE: SPQ_STAGE_ACTIVATIONS)
+constexpr unsigned kkey(int a, int b = 0, int c = 0, int d = 0, int e = 0) { return (unsigned)(a | (b << 8) | (c << 12) | (d << 16) | (e << 20)); }
+template <class... A> struct Kernel { unsigned key; void (*fn)(A...); int lds; };
+template <class... A> struct Family {
+  int group;                                               // bit of g_dev_attr; -1: no dynamic LDS, nothing to raise
+  const char* what;
+  const Kernel<A...>* rows; int n;
+  const Kernel<A...>* find(unsigned key) const {
+    for (int i = 0; i < n; ++i) if (rows[i].key == key) return rows + i;
+    return nullptr;
   }
-  if (a->lora_on_fq_input) { set_error("spq_linear_lora_fwd: SPQ_PATH_FP6 has no lora_on_fq_input form (the LoRA branch reads the raw x)"); return SPQ_ERR_UNSUPPORTED; }
-  if (a->out_levels || a->out_levels_lo) { set_error("spq_linear_lora_fwd: SPQ_PATH_FP6 has no levels-out store"); return SPQ_ERR_UNSUPPORTED; }
-  if (a->epilogue != SPQ_EPILOGUE_NONE && a->epilogue != SPQ_EPILOGUE_GELU) { set_error("spq_linear_lora_fwd: SPQ_PATH_FP6 epilogue %d unknown", a->epilogue); return SPQ_ERR_UNSUPPORTED; }
-  if (a->epilogue == SPQ_EPILOGUE_GELU && (a->N & 3) != 0) { set_error("spq_linear_lora_fwd: the fused GELU epilogue needs N %% 4 == 0 (got N=%lld)", (long long)a->N); return SPQ_ERR_UNSUPPORTED; }
-  if (a->r > 128) { set_error("spq_linear_lora_fwd: SPQ_PATH_FP6 needs LoRA rank <= 128 (got r=%lld)", (long long)a->r); return SPQ_ERR_UNSUPPORTED; }
-  return SPQ_OK;
+  int raise_lds() const {
+    if (group < 0) return SPQ_OK;
+    AttrOnce once(group);
+    int rc = SPQ_OK;
+    for (int i = 0; once.first && i < n; ++i) {
+      const hipError_t e = hipFuncSetAttribute((const void*)rows[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, rows[i].lds);
+      if (e != hipSuccess && rc == SPQ_OK) { set_error("hipFuncSetAttribute(%sLDS %d B): %s", what, rows[i].lds, hipGetErrorString(e)); rc = SPQ_ERR_LAUNCH; }
+    }
+    return rc;
+  }
+  void launch(unsigned key, unsigned grid, unsigned block, hipStream_t st, const A&... args) const {   // (fwd_validate found the row)
+    const Kernel<A...>* k = find(key);
+    (*k->fn)<<<grid, block, k->lds, st>>>(args...);
+  }
+};
+#define SPQ_ROW(KERNEL, LDS, ...) {kkey(__VA_ARGS__), KERNEL<__VA_ARGS__>, LDS}   // the key IS the template argument list
+#define SPQ_FAMILY(GROUP, WHAT, ROWS) {GROUP, WHAT, ROWS, (int)(sizeof(ROWS) / sizeof(ROWS[0]))}
+
+// activation pass.  generic <column tiles of t>; panel <chunks>; streaming <rows, store form, LayerNorm>, store form 0: fp16 levels,
+// 2: int8 levels, 3: two fp16 limbs, 4: packed e2m3 (FP6); streaming + preparation workgroups <rows, store form, int8 weight plane>
+// (rows and tables in the order the instantiations have always had in the code object)
+static const Kernel<XPassArgs> kXPanelRows[] = {SPQ_ROW(xpass_panel_kernel, XP_LDS, XP_CHUNKS),
+                                                SPQ_ROW(xpass_panel_kernel, xp_lds(XP_CHUNKS_SMALL), XP_CHUNKS_SMALL)};
+#define SPQ_XS_ROW(R, A8, LN) SPQ_ROW(xpass_stream_kernel, xs_lds(R), R, A8, LN)
+#define SPQ_XS_LEVELS(R, LN) SPQ_XS_ROW(R, 0, LN), SPQ_XS_ROW(R, 2, LN)
+#define SPQ_XS_PACKED(A8, LN) SPQ_XS_ROW(16, A8, LN), SPQ_XS_ROW(32, A8, LN)
+static const Kernel<XPassArgs> kXStreamRows[] = {SPQ_XS_LEVELS(16, false), SPQ_XS_LEVELS(16, true), SPQ_XS_LEVELS(32, false), SPQ_XS_LEVELS(32, true),
+                                                 SPQ_XS_PACKED(3, false), SPQ_XS_PACKED(3, true), SPQ_XS_PACKED(4, false), SPQ_XS_PACKED(4, true)};
+#define SPQ_XSP_ROW(R, A8, MODE) SPQ_ROW(xpass_stream_prep_kernel, xs_lds(R), R, A8, MODE)
+static const Kernel<XPassArgs, PrepArgs, int> kXStreamPrepRows[] = {SPQ_XSP_ROW(16, 0, 0), SPQ_XSP_ROW(16, 2, 1), SPQ_XSP_ROW(32, 0, 0),
+                                                                    SPQ_XSP_ROW(32, 2, 1), SPQ_XSP_ROW(16, 3, 0), SPQ_XSP_ROW(32, 3, 0)};
+static const Kernel<XPassArgs> kXGenericRows[] = {SPQ_ROW(xpass_kernel, 0, 2), SPQ_ROW(xpass_kernel, 0, 4)};
+static const Family<XPassArgs> kXGeneric = SPQ_FAMILY(-1, "xpass ", kXGenericRows), kXPanel = SPQ_FAMILY(0, "xpass ", kXPanelRows),
+                               kXStream = SPQ_FAMILY(7, "xpass ", kXStreamRows);
+static const Family<XPassArgs, PrepArgs, int> kXStreamPrep = SPQ_FAMILY(8, "xpass ", kXStreamPrepRows);
+static const Family<XPassArgs>& x_family(int kind) { return kind == X_GENERIC ? kXGeneric : kind == X_PANEL ? kXPanel : kXStream; }   // (not X_STREAM_PREP)
+
+// contraction.  FP6 <EPI, RAG>; int8 (64-deep ring <NL, V, EPI>, 128-deep stages <NL, EPI>: the key is {k128, EPI});
+// f16 limbs <AL, EPI, LV, SK, RAG>: ONE kernel for every shape (128 x 128 tiles, three workgroups per CU); the 256 x 128
+// persistent kernels of round 1 live in tools/variants/gemm_256x128.h (measured slower at every shape of SURVEY 8(d): config 3
+// 1.466 -> 1.356 ms, config 5 27.8 -> 27.4 ms)
+static const Kernel<GemmFp6Args> kGemmFp6Rows[] = {SPQ_ROW(gemm_fp6_kernel, F6_LDS, 0, false), SPQ_ROW(gemm_fp6_kernel, F6_LDS, 1, false),
+                                                   SPQ_ROW(gemm_fp6_kernel, F6_LDS, 0, true)};
+static const Kernel<GemmI8Args> kGemmI8Rows[] = {{kkey(0, 0), gemm_i8_kernel<1, 0, 0>, I8_LDS}, {kkey(0, 1), gemm_i8_kernel<1, 0, 1>, I8_LDS},
+                                                 {kkey(1, 0), gemm_i8_k128_kernel<1, 0>, i8k_lds(1)}, {kkey(1, 1), gemm_i8_k128_kernel<1, 1>, i8k_lds(1)}};
+#define SPQ_T128_ROWS(EPI, LV, SK, RAG) SPQ_ROW(gemm_f16x2_t128_kernel, T128_LDS, 1, EPI, LV, SK, RAG), SPQ_ROW(gemm_f16x2_t128_kernel, T128_LDS, 2, EPI, LV, SK, RAG)
+static const Kernel<GemmF16Args> kGemmT128Rows[] = {SPQ_T128_ROWS(0, 0, false, false), SPQ_T128_ROWS(1, 0, false, false), SPQ_T128_ROWS(0, 1, false, false),
+                                                    SPQ_T128_ROWS(1, 1, false, false), SPQ_T128_ROWS(0, 2, false, false), SPQ_T128_ROWS(1, 2, false, false),
+                                                    SPQ_T128_ROWS(0, 0, true, false), SPQ_T128_ROWS(0, 0, false, true)};
+#undef SPQ_T128_ROWS
+static const Family<GemmFp6Args> kGemmFp6 = SPQ_FAMILY(9, "", kGemmFp6Rows);
+static const Family<GemmI8Args> kGemmI8 = SPQ_FAMILY(1, "", kGemmI8Rows);
+static const Family<GemmF16Args> kGemmT128 = SPQ_FAMILY(3, "", kGemmT128Rows);
+#undef SPQ_FAMILY
+#undef SPQ_ROW
+#undef SPQ_XS_ROW
+#undef SPQ_XS_LEVELS
+#undef SPQ_XS_PACKED
+#undef SPQ_XSP_ROW
+
+// ---- plan: what one spq_linear_lora_fwd call on the limb / int8 / FP6 paths will run (x_kind, g_kind: the enums above) -------------
+struct FwdPlan {
+  bool panel_ok, stream_ok;                                // what the panel / streaming activation kernels need (the refusals read them)
+  int x_kind; unsigned x_key, x_grid, x_block, x_nx;       // x_nx: activation workgroups of X_STREAM_PREP (the rest prepare weight rows)
+  int at_blocks;                                           // > 0: FQ(A)^T goes first as a launch of its own (X_STREAM_PREP consumes it)
+  bool prep_launch;                                        // a->prepare served by the ordinary preparation launch, issued first
+  int sk; int64_t sk_tiles;                                // split-K factor of the f16-limb contraction, {tickets, done} pairs to zero
+  bool sk_zero_in_xpass;                                   // the streaming activation launch zeroes them; else hipMemsetAsync
+  int g_kind; unsigned g_key, g_grid, g_block;
+};
+
+static bool prep_wave_ok(const spq_prepare_args* q) {      // the one-wave-per-row preparation kernel applies
+  return q->path != SPQ_PATH_FP6 && (q->K % 4 == 0) && q->K <= 4 * 64 * PREP_MAXI && aligned16(q->W) && (!q->x_per_channel || aligned16(q->sx)) &&
+         q->r <= 128;
+}
+static int prep_at_blocks(const spq_prepare_args* q) {     // 32 x 32 tiles of FQ(A)^T (A == NULL: it is made elsewhere)
+  return (q->r > 0 && q->A) ? (int)(((q->r + 31) / 32) * ((q->K + 31) / 32)) : 0;
 }
 
-int fwd_f16x2(const spq_fwd_args* a, hipStream_t st) {
-  const bool x3 = a->path == SPQ_PATH_F16X3;
-  const int i8nl = i8_limbs_of(a->path);
-  const bool fp6 = a->path == SPQ_PATH_FP6;
-  if (fp6) {                                               // (fp6_validate ran in spq_linear_lora_fwd, the only caller)
-    if (a->prepare && a->prepare->path != a->path) { set_error("spq_linear_lora_fwd: prepare args are for another operand path"); return SPQ_ERR_INVALID; }
-  } else if (i8nl) {
-    if (!(a->quantize_input && a->qtype == SPQ_MINMAX && a->symmetric && a->bits >= 2 && a->bits <= 8)) {
-      set_error("spq_linear_lora_fwd: the int8 operand paths need a symmetric minmax input quantizer with 2..8 bits "
-                "(got qtype=%d symmetric=%d bits=%d quantize_input=%d)", a->qtype, a->symmetric, a->bits, a->quantize_input);
-      return SPQ_ERR_UNSUPPORTED;
-    }
-    if (a->x_per_channel) { set_error("spq_linear_lora_fwd: SPQ_PATH_I8 needs a per-tensor input scale"); return SPQ_ERR_UNSUPPORTED; }
-    if (a->prepare && a->prepare->path != a->path) { set_error("spq_linear_lora_fwd: prepare args are for another operand path"); return SPQ_ERR_INVALID; }
-  } else if (x3) {
-    if (!((!a->quantize_input || (a->bits >= 1 && a->bits <= 24)) && a->x_limb_scale)) {
-      set_error("spq_linear_lora_fwd: SPQ_PATH_F16X3 needs x_limb_scale (and 1..24 bits when quantize_input is set)");
-      return SPQ_ERR_UNSUPPORTED;
-    }
-  } else if (!(a->quantize_input && a->qtype == SPQ_MINMAX && a->symmetric && a->bits >= 2 && a->bits <= 12)) {
-    set_error("spq_linear_lora_fwd: SPQ_PATH_F16X2 needs a symmetric minmax input quantizer with 2..12 bits "
-              "(got qtype=%d symmetric=%d bits=%d quantize_input=%d)", a->qtype, a->symmetric, a->bits, a->quantize_input);
-    return SPQ_ERR_UNSUPPORTED;
-  }
-  if (!f16x2_shape_ok(a->M, a->K, a->N, a->r)) {
-    set_error("spq_linear_lora_fwd: the F16 operand paths need LoRA rank <= 128 (got r=%lld)", (long long)a->r);
-    return SPQ_ERR_UNSUPPORTED;
-  }
-  SPQ_REQUIRE(a->w_rowscale, "spq_linear_lora_fwd: w_rowscale missing for SPQ_PATH_F16X2");
-  const F16x2Layout L = make_layout(a->M, a->K, a->r, fp6 ? 0 : a->N, x3 ? 2 : i8nl ? -1 : 1);
-  const PrepLayout P = make_prep_layout(a->N, a->K, a->r);
-  char* ws = (char*)a->workspace;
-  const char* wp = (const char*)a->w_prep;
-
-  XPassArgs x;
-  x.x = a->x; x.sx = a->sx; x.zx = a->zx; x.aT = a->a_prep;
-  x.qx = (_Float16*)(ws + L.off_qx); x.thi = (_Float16*)(ws + L.off_thi); x.tlo = (_Float16*)(ws + L.off_tlo);
-  x.rowinv = (float*)(ws + L.off_rowinv);
-  x.M = (int)a->M; x.K = (int)a->K; x.r = (int)a->r; x.Kp = (int)L.Kp; x.Rp = (int)L.Rp;
-  x.x_pc = a->x_per_channel; x.bits = a->bits;
-  x.limbs = x3 ? 1 : 0; x.qtype = a->qtype; x.symmetric = a->symmetric;
-  if (x3 && !a->quantize_input) {   // identity quantizer: limbs of x itself; the scale loads read a valid dummy
-    x.bits = 32; x.qtype = SPQ_MINMAX; x.symmetric = 1; x.x_pc = 0; x.sx = a->x_limb_scale; x.zx = a->x_limb_scale;
-  }
-  x.xl = (_Float16*)(ws + L.off_xl); x.xscale = a->x_limb_scale;
-  x.t_out = (a->r > 0) ? a->t_out : nullptr;
-  x.lora_fq = (a->lora_on_fq_input && a->quantize_input) ? 1 : 0;
-  x.ln_w = a->ln_weight; x.ln_b = a->ln_bias; x.ln_eps = a->ln_eps;
-  const bool lora_up = a->r > 0 && a->b_prep != nullptr;     // r > 0 without b_prep: LoRA-down only (t_out)
-  if (a->path == SPQ_PATH_U8X2) {
-    set_error("spq_linear_lora_fwd: SPQ_PATH_U8X2 (byte-level ring kernel) was measured slower than SPQ_PATH_F16X2 and is no longer in the library "
-              "(tools/variants/gemm_u8x2.h); use SPQ_PATH_F16X2 -- same prepared operands, same result");
-    return SPQ_ERR_UNSUPPORTED;
-  }
-  if (a->a_limb_scale) {
-    set_error("spq_linear_lora_fwd: a_limb_scale (LoRA-down on the f16 pipe, tools/variants/xpass_panel16.h) is no longer in the library; pass null");
-    return SPQ_ERR_UNSUPPORTED;
-  }
-  x.a8 = fp6 ? 4 : i8nl ? 2 : 0;
-  x.a6 = (unsigned char*)(ws + L.off_qx); x.kb6 = (int)((a->K + 127) / 128);
-  const unsigned xgrid = (unsigned)((a->M + XR - 1) / XR);
-  const bool panel_ok = (a->K % 64 == 0) && L.Rp <= 64 && aligned16(a->x) && (a->r == 0 || aligned16(a->a_prep)) && aligned16(x.sx) &&
-                        aligned16(x.zx);
+// Pure host logic: (arguments, switches, CU count) -> plan.  Expects arguments that passed the checks in front of it in fwd_validate.
+static FwdPlan fwd_plan(const spq_fwd_args* a, const Switches& sw, int cus) {
+  FwdPlan p = {};
+  const bool x3 = a->path == SPQ_PATH_F16X3, i8 = i8_limbs_of(a->path) != 0, fp6 = a->path == SPQ_PATH_FP6;
   const bool do_xpass = a->stage != SPQ_STAGE_CONTRACTION, do_gemm = a->stage != SPQ_STAGE_ACTIVATIONS;
-  // a->prepare: the weight-side operands are (re)made by this call.  Where the streaming activation kernel runs, the row work
-  // goes into ITS launch as extra workgroups (xpass_stream_prep_kernel; FQ(A)^T, which the pass itself consumes, goes first as a
-  // launch of a few dozen workgroups; SPQ_PREP_ROLE=0 turns that off); otherwise the ordinary preparation launch is issued first
-  // (SPQ_PREP_INPASS=1: the earlier variant that spreads the rows over the 16-row activation kernel's own workgroups).
-  PrepArgs pa;
-  int at_blocks = 0;
-  const Switches sw = g_switches;
-  // split-K of the contraction (f16 limb kernels): decided here because the activation launch zeroes its counters
-  int sk = 1;
-  const int64_t sk_nwg = (L.Mp / 128) * (P.Np / GN);
-  if (!i8nl && !fp6 && do_gemm && a->epilogue == SPQ_EPILOGUE_NONE && !a->out_levels && (a->N & 3) == 0) {
-    const int nl = lora_up ? (int)(L.Rp / GK) * 2 : 0;
-    const int T = nl + (x3 ? 2 : 1) * (int)(L.Kp / GK);
-    sk = t128_split(sk_nwg, T, nl, (int64_t)T128_WGS * gemm_grid(1 << 30), sw.split_k);
-    if (sk > 1 && sk_nwg * sk > sk_reserve_units(a->M, a->K, a->N, a->r, x3 ? 2 : 1)) sk = 1;   // (cannot happen: the reserve is the maximum over the cases)
-  }
-  bool sk_zeroed = false;
-  x.zero_ptr = nullptr; x.zero_n = 0;
-  const int stream16 = sw.stream;
-  const bool stream_ok = panel_ok && stream16 && a->r > 0 && (!x.limbs || (sw.stream_limbs && a->quantize_input)) && !x.lora_fq;
-  bool role_prep = false;                                  // the row work as extra workgroups of the streaming activation launch
-  if (a->prepare && do_xpass) {
-    bool wave_ok = false;
-    int prc = prepare_fill(a->prepare, pa, at_blocks, wave_ok);
-    if (prc) return prc;
-    if (a->prepare->N != a->N || a->prepare->K != a->K || a->prepare->r < a->r) { set_error("spq_linear_lora_fwd: prepare args describe another layer"); return SPQ_ERR_INVALID; }
-    if (sw.prep_role && !fp6 && stream_ok && !a->ln_weight && wave_ok && a->K <= 1024) {
-      role_prep = true;
-      if (at_blocks) {
-        fq_transpose_kernel<<<(unsigned)at_blocks, 256, 0, st>>>(pa);
-        prc = check_launch("spq_linear_lora_fwd(FQ(A)^T)");
-        if (prc) return prc;
-      }
-    } else {
-      prc = spq_prepare_f16x2_args(a->prepare, (spq_stream_t)st);
-      if (prc) return prc;
+  const int64_t Mp = pad_to(a->M, GM), Np = pad_to(a->N, GN), Kp = pad_to(a->K, GK), Rp = a->r > 0 ? pad_to(a->r, GK) : 0;
+  const bool gelu = a->epilogue == SPQ_EPILOGUE_GELU, ragged = (a->N & 3) != 0;   // ragged: rows of y not 16-B aligned, scalar stores
+  const float* sx = (x3 && !a->quantize_input) ? a->x_limb_scale : a->sx;         // (identity quantizer: see fill_xpass)
+  const float* zx = (x3 && !a->quantize_input) ? a->x_limb_scale : a->zx;
+  p.panel_ok = (a->K % 64 == 0) && Rp <= 64 && aligned16(a->x) && (a->r == 0 || aligned16(a->a_prep)) && aligned16(sx) && aligned16(zx);
+  p.stream_ok = p.panel_ok && sw.stream && a->r > 0 && (!x3 || (sw.stream_limbs && a->quantize_input)) &&
+                !(a->lora_on_fq_input && a->quantize_input);
+  p.sk = 1; p.sk_tiles = t128_tiles(a->M, a->N);
+  if (do_gemm && fp6) {
+    p.g_kind = G_FP6; p.g_key = kkey(gelu, ragged); p.g_block = 256;
+    p.g_grid = (unsigned)std::min<int64_t>((Mp / 128) * (Np / 128), 3 * (int64_t)cus);
+  } else if (do_gemm && i8) {
+    // 128-deep stages (whole cache lines, half as many stages: measured 50-53 us against 56-59 at the c_fc shape) whenever K
+    // allows; the 64-deep ring kernel otherwise
+    const bool k128 = (Kp % 128) == 0;
+    const int64_t tiles = (Mp / GM) * (Np / GN);
+    p.g_kind = G_I8; p.g_key = kkey(k128, gelu); p.g_block = k128 ? 256 : I8_THREADS;
+    p.g_grid = (unsigned)(k128 ? std::min<int64_t>(2 * tiles, 2 * (int64_t)cus) : std::min<int64_t>(tiles, cus));
+  } else if (do_gemm) {
+    const int al = x3 ? 2 : 1, lv = !a->out_levels ? 0 : a->out_levels_lo ? 2 : 1;
+    // split-K: the plain epilogue only; decided here because the activation launch zeroes its counters
+    if (a->epilogue == SPQ_EPILOGUE_NONE && !lv && !ragged) {
+      p.sk = t128_split_of(a->M, a->K, a->N, a->b_prep ? a->r : 0, al, cus, sw.split_k);   // (r > 0 without b_prep: LoRA-down only)
+      if (p.sk > 1 && p.sk_tiles * p.sk > sk_reserve_units(a->M, a->K, a->N, a->r, al)) p.sk = 1;   // (cannot happen: the reserve is the maximum over the cases)
     }
-  } else if (a->prepare && !do_xpass) {
-    set_error("spq_linear_lora_fwd: prepare args go with the activation stage");
-    return SPQ_ERR_INVALID;
+    p.g_kind = G_T128; p.g_key = kkey(al, gelu, lv, p.sk > 1, ragged); p.g_block = 256;
+    p.g_grid = (unsigned)std::min<int64_t>(2 * (Mp / GM) * (Np / GN) * p.sk, (int64_t)(p.sk > 1 ? 2 : 1) * T128_WGS * cus);   // split-K: one unit per workgroup
   }
+  if (!do_xpass) return p;                                 // the activation pass of this call ran earlier (same arguments, same workspace)
+  const unsigned xgrid = (unsigned)((a->M + XR - 1) / XR);
+  if (p.stream_ok) {
+    // 32-row workgroups halve the FQ(A)^T traffic through L2; taken once they still cover every CU
+    const int R = (sw.stream == 32 || (sw.stream != 16 && (a->M + 31) / 32 >= cus)) ? 32 : 16;
+    const int form = x3 ? 3 : fp6 ? 4 : i8 ? 2 : 0;
+    p.x_grid = p.x_nx = (unsigned)((a->M + R - 1) / R); p.x_block = (unsigned)R * 16;
+    p.sk_zero_in_xpass = p.sk > 1;
+    // a->prepare: the row work goes into THIS launch as extra workgroups; FQ(A)^T, which the pass itself consumes, goes first
+    if (a->prepare && sw.prep_role && !fp6 && !a->ln_weight && prep_wave_ok(a->prepare) && a->K <= 1024) {
+      p.x_kind = X_STREAM_PREP; p.x_key = kkey(R, form, form == 2);
+      p.x_grid += (unsigned)((Np + R / 4 - 1) / (R / 4));
+      p.at_blocks = prep_at_blocks(a->prepare);
+    } else { p.x_kind = X_STREAM; p.x_key = kkey(R, form, a->ln_weight != nullptr); }
+  } else if (p.panel_ok && !fp6) {                         // (FP6 store form: the streaming kernel, or the generic kernel below)
+    p.x_kind = X_PANEL; p.x_key = kkey(xgrid >= 2 * (unsigned)cus ? XP_CHUNKS_SMALL : XP_CHUNKS); p.x_grid = xgrid; p.x_block = 512;
+  } else { p.x_kind = X_GENERIC; p.x_key = kkey(Rp <= 64 ? 2 : 4); p.x_grid = xgrid; p.x_block = 256; }
+  p.prep_launch = a->prepare && p.x_kind != X_STREAM_PREP;
+  return p;
+}
+
+// ---- validate: every refusal of spq_linear_lora_fwd on these paths, before anything is enqueued.  Several refusals depend on what
+// would run, so the plan is made here, half way down, and handed back with the PrepArgs of a->prepare: the launch takes both as they are.
+int fwd_check_common(const spq_fwd_args* a);               // spq_api.hip: the checks every operand path shares
+int prepare_fill(const spq_prepare_args* q, PrepArgs& a);
+#define SPQ_REFUSE(...) do { set_error(__VA_ARGS__); return SPQ_ERR_UNSUPPORTED; } while (0)
+
+static int fwd_validate(const spq_fwd_args* a, const Switches& sw, FwdPlan& p, PrepArgs& pa) {
+  const bool x3 = a->path == SPQ_PATH_F16X3, i8 = i8_limbs_of(a->path) != 0, fp6 = a->path == SPQ_PATH_FP6;
+  const bool minmax_sym = a->quantize_input && a->qtype == SPQ_MINMAX && a->symmetric;
+  if (fp6) {                                               // what SPQ_PATH_FP6 cannot serve: refused before any pointer is looked at
+    if (!(minmax_sym && a->bits >= 2 && a->bits <= 4))
+      SPQ_REFUSE("spq_linear_lora_fwd: SPQ_PATH_FP6 needs a symmetric minmax input quantizer with 2..4 bits "
+                 "(got qtype=%d symmetric=%d bits=%d quantize_input=%d)", a->qtype, a->symmetric, a->bits, a->quantize_input);
+    if (a->lora_on_fq_input) SPQ_REFUSE("spq_linear_lora_fwd: SPQ_PATH_FP6 has no lora_on_fq_input form (the LoRA branch reads the raw x)");
+    if (a->out_levels || a->out_levels_lo) SPQ_REFUSE("spq_linear_lora_fwd: SPQ_PATH_FP6 has no levels-out store");
+    if (a->epilogue != SPQ_EPILOGUE_NONE && a->epilogue != SPQ_EPILOGUE_GELU) SPQ_REFUSE("spq_linear_lora_fwd: SPQ_PATH_FP6 epilogue %d unknown", a->epilogue);
+    if (a->epilogue == SPQ_EPILOGUE_GELU && (a->N & 3) != 0) SPQ_REFUSE("spq_linear_lora_fwd: the fused GELU epilogue needs N %% 4 == 0 (got N=%lld)", (long long)a->N);
+    if (a->r > 128) SPQ_REFUSE("spq_linear_lora_fwd: SPQ_PATH_FP6 needs LoRA rank <= 128 (got r=%lld)", (long long)a->r);
+  }
+  int rc = fwd_check_common(a);
+  if (rc) return rc;
+  if (i8) {
+    if (!(minmax_sym && a->bits >= 2 && a->bits <= 8))
+      SPQ_REFUSE("spq_linear_lora_fwd: the int8 operand paths need a symmetric minmax input quantizer with 2..8 bits "
+                 "(got qtype=%d symmetric=%d bits=%d quantize_input=%d)", a->qtype, a->symmetric, a->bits, a->quantize_input);
+    if (a->x_per_channel) SPQ_REFUSE("spq_linear_lora_fwd: SPQ_PATH_I8 needs a per-tensor input scale");
+  } else if (x3) {
+    if (!((!a->quantize_input || (a->bits >= 1 && a->bits <= 24)) && a->x_limb_scale))
+      SPQ_REFUSE("spq_linear_lora_fwd: SPQ_PATH_F16X3 needs x_limb_scale (and 1..24 bits when quantize_input is set)");
+  } else if (!fp6 && !(minmax_sym && a->bits >= 2 && a->bits <= 12))
+    SPQ_REFUSE("spq_linear_lora_fwd: SPQ_PATH_F16X2 needs a symmetric minmax input quantizer with 2..12 bits "
+               "(got qtype=%d symmetric=%d bits=%d quantize_input=%d)", a->qtype, a->symmetric, a->bits, a->quantize_input);
+  SPQ_REQUIRE(!(fp6 || i8) || !a->prepare || a->prepare->path == a->path, "spq_linear_lora_fwd: prepare args are for another operand path");
+  if (!f16x2_shape_ok(a->M, a->K, a->N, a->r)) SPQ_REFUSE("spq_linear_lora_fwd: the F16 operand paths need LoRA rank <= 128 (got r=%lld)", (long long)a->r);
+  SPQ_REQUIRE(a->w_rowscale, "spq_linear_lora_fwd: w_rowscale missing for SPQ_PATH_F16X2");
+  if (a->path == SPQ_PATH_U8X2)
+    SPQ_REFUSE("spq_linear_lora_fwd: SPQ_PATH_U8X2 (byte-level ring kernel) was measured slower than SPQ_PATH_F16X2 and is no longer in the library "
+               "(tools/variants/gemm_u8x2.h); use SPQ_PATH_F16X2 -- same prepared operands, same result");
+  if (a->a_limb_scale)
+    SPQ_REFUSE("spq_linear_lora_fwd: a_limb_scale (LoRA-down on the f16 pipe, tools/variants/xpass_panel16.h) is no longer in the library; pass null");
+  const bool do_xpass = a->stage != SPQ_STAGE_CONTRACTION;
+  if (a->prepare) {                                        // the weight-side operands are (re)made by this call
+    SPQ_REQUIRE(do_xpass, "spq_linear_lora_fwd: prepare args go with the activation stage");
+    if ((rc = prepare_fill(a->prepare, pa))) return rc;
+    SPQ_REQUIRE(a->prepare->N == a->N && a->prepare->K == a->K && a->prepare->r >= a->r, "spq_linear_lora_fwd: prepare args describe another layer");
+  }
+  p = fwd_plan(a, sw, (int)gemm_grid(1 << 30));
   if (a->ln_weight && do_xpass) {
     // the LayerNorm prologue lives in the panel and streaming kernels (fp32-MFMA LoRA-down), rows of at most 1024 elements; the FP6
     // store form exists in the streaming kernel only
-    if (fp6 && panel_ok && !stream_ok) {
-      set_error("spq_linear_lora_fwd: SPQ_PATH_FP6 + LayerNorm prologue needs the streaming activation kernel (rank > 0, SPQ_XPASS_STREAM not 0); "
-                "run spq_layernorm first");
-      return SPQ_ERR_UNSUPPORTED;
-    }
-    if (!a->ln_bias || !panel_ok || (fp6 && !stream_ok) || a->K > 1024 || !aligned16(a->ln_weight) || !aligned16(a->ln_bias)) {
-      set_error("spq_linear_lora_fwd: the LayerNorm prologue needs K %% 64 == 0, K <= 1024, rank <= 64 and 16-byte aligned operands");
-      return SPQ_ERR_UNSUPPORTED;
-    }
+    if (fp6 && p.panel_ok && !p.stream_ok)
+      SPQ_REFUSE("spq_linear_lora_fwd: SPQ_PATH_FP6 + LayerNorm prologue needs the streaming activation kernel (rank > 0, SPQ_XPASS_STREAM not 0); "
+                 "run spq_layernorm first");
+    if (!a->ln_bias || !p.panel_ok || (fp6 && !p.stream_ok) || a->K > 1024 || !aligned16(a->ln_weight) || !aligned16(a->ln_bias))
+      SPQ_REFUSE("spq_linear_lora_fwd: the LayerNorm prologue needs K %% 64 == 0, K <= 1024, rank <= 64 and 16-byte aligned operands");
   }
-  if (!do_xpass) {
-    // the activation pass of this call ran earlier (same arguments, same workspace)
-  } else if (panel_ok && (!fp6 || stream_ok)) {           // (FP6 store form: the streaming kernel, or the generic kernel below)
-    if (AttrOnce once(0); once.first) {
-      hipError_t e = hipFuncSetAttribute((const void*)xpass_panel_kernel<XP_CHUNKS>, hipFuncAttributeMaxDynamicSharedMemorySize, XP_LDS);
-      if (e != hipSuccess) { set_error("hipFuncSetAttribute(xpass LDS %d B): %s", XP_LDS, hipGetErrorString(e)); return SPQ_ERR_LAUNCH; }
-      (void)hipFuncSetAttribute((const void*)xpass_panel_kernel<XP_CHUNKS_SMALL>, hipFuncAttributeMaxDynamicSharedMemorySize, xp_lds(XP_CHUNKS_SMALL));
-    }
-    if (stream_ok) {
-      if (sk > 1) { x.zero_ptr = (int*)(ws + L.off_skcnt); x.zero_n = (int)(2 * sk_nwg); sk_zeroed = true; }
-      if (AttrOnce once(7); once.first) {
-#define SPQ_XS_ATTR(R, A8, LN) (void)hipFuncSetAttribute((const void*)xpass_stream_kernel<R, A8, LN>, hipFuncAttributeMaxDynamicSharedMemorySize, xs_lds(R))
-        SPQ_XS_ATTR(16, 0, false); SPQ_XS_ATTR(16, 2, false); SPQ_XS_ATTR(16, 0, true); SPQ_XS_ATTR(16, 2, true);
-        SPQ_XS_ATTR(32, 0, false); SPQ_XS_ATTR(32, 2, false); SPQ_XS_ATTR(32, 0, true); SPQ_XS_ATTR(32, 2, true);
-        SPQ_XS_ATTR(16, 3, false); SPQ_XS_ATTR(32, 3, false); SPQ_XS_ATTR(16, 3, true); SPQ_XS_ATTR(32, 3, true);
-        SPQ_XS_ATTR(16, 4, false); SPQ_XS_ATTR(32, 4, false); SPQ_XS_ATTR(16, 4, true); SPQ_XS_ATTR(32, 4, true);
-#undef SPQ_XS_ATTR
-      }
-      // 32-row workgroups halve the FQ(A)^T traffic through L2; taken once they still cover every CU
-      const bool r32 = stream16 == 32 || (stream16 != 16 && (a->M + 31) / 32 >= gemm_grid(1 << 30));
-      const bool ln = x.ln_w != nullptr;
-      if (role_prep) {
-        if (AttrOnce once(8); once.first) {
-#define SPQ_XSP_ATTR(R, A8, MODE) (void)hipFuncSetAttribute((const void*)xpass_stream_prep_kernel<R, A8, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, xs_lds(R))
-          SPQ_XSP_ATTR(16, 0, 0); SPQ_XSP_ATTR(16, 2, 1); SPQ_XSP_ATTR(32, 0, 0); SPQ_XSP_ATTR(32, 2, 1); SPQ_XSP_ATTR(16, 3, 0); SPQ_XSP_ATTR(32, 3, 0);
-#undef SPQ_XSP_ATTR
-        }
-        const int R = r32 ? 32 : 16;
-        const unsigned nx = (unsigned)((a->M + R - 1) / R);
-        const unsigned nrow = (unsigned)((pad_to(a->N, GN) + R / 4 - 1) / (R / 4));
-#define SPQ_XSP_LAUNCH(R, A8, MODE) xpass_stream_prep_kernel<R, A8, MODE><<<nx + nrow, R * 16, xs_lds(R), st>>>(x, pa, (int)nx)
-        if (x.limbs) { if (r32) SPQ_XSP_LAUNCH(32, 3, 0); else SPQ_XSP_LAUNCH(16, 3, 0); }
-        else if (r32) { if (x.a8 == 0) SPQ_XSP_LAUNCH(32, 0, 0); else SPQ_XSP_LAUNCH(32, 2, 1); }
-        else { if (x.a8 == 0) SPQ_XSP_LAUNCH(16, 0, 0); else SPQ_XSP_LAUNCH(16, 2, 1); }
-#undef SPQ_XSP_LAUNCH
-      } else {
-#define SPQ_XS_LAUNCH(R, A8, LN) xpass_stream_kernel<R, A8, LN><<<(unsigned)((a->M + R - 1) / R), R * 16, xs_lds(R), st>>>(x)
-#define SPQ_XS_PICK(R) do { if (ln) { if (x.a8 == 0) SPQ_XS_LAUNCH(R, 0, true); else SPQ_XS_LAUNCH(R, 2, true); } \
-                            else { if (x.a8 == 0) SPQ_XS_LAUNCH(R, 0, false); else SPQ_XS_LAUNCH(R, 2, false); } } while (0)
-        if (fp6) { if (ln) { if (r32) SPQ_XS_LAUNCH(32, 4, true); else SPQ_XS_LAUNCH(16, 4, true); } else { if (r32) SPQ_XS_LAUNCH(32, 4, false); else SPQ_XS_LAUNCH(16, 4, false); } }
-        else if (x.limbs && ln) { if (r32) SPQ_XS_LAUNCH(32, 3, true); else SPQ_XS_LAUNCH(16, 3, true); }
-        else if (x.limbs) { if (r32) SPQ_XS_LAUNCH(32, 3, false); else SPQ_XS_LAUNCH(16, 3, false); }
-        else if (r32) SPQ_XS_PICK(32); else SPQ_XS_PICK(16);
-#undef SPQ_XS_PICK
-#undef SPQ_XS_LAUNCH
-      }
-    } else if (xgrid >= 2 * gemm_grid(1 << 30)) xpass_panel_kernel<XP_CHUNKS_SMALL><<<xgrid, 512, xp_lds(XP_CHUNKS_SMALL), st>>>(x);
-    else xpass_panel_kernel<XP_CHUNKS><<<xgrid, 512, XP_LDS, st>>>(x);
-  } else if (L.Rp <= 64) xpass_kernel<2><<<xgrid, 256, 0, st>>>(x);
-  else xpass_kernel<4><<<xgrid, 256, 0, st>>>(x);
-  int rc = check_launch("spq_linear_lora_fwd(xpass)");
-  if (rc || !do_gemm) return rc;
-
-  if (fp6) {
-    const PrepLayoutFp6 P6 = make_prep_layout_fp6(a->N, a->K, a->r);
-    GemmFp6Args q;
-    q.A6 = x.a6; q.W6 = (const unsigned char*)wp; q.plane_stride = (int64_t)P6.plane;
-    q.rowscale = a->w_rowscale; q.bfac = (const float*)(wp + P6.off_bfac); q.bias = a->bias; q.y = a->y;
-    q.M = (int)a->M; q.N = (int)a->N; q.KB = (int)P6.KB; q.tiles_m = (int)(L.Mp / 128); q.tiles_n = (int)(P6.Np / 128);
-    q.thi = x.thi; q.tlo = x.tlo; q.Bhi = (const _Float16*)(wp + P6.off_bhi); q.Blo = (const _Float16*)(wp + P6.off_blo);
-    q.rowinv = x.rowinv; q.Rp = lora_up ? (int)L.Rp : 0;
-    if (AttrOnce once(9); once.first) {
-      hipError_t e = hipFuncSetAttribute((const void*)gemm_fp6_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, F6_LDS);
-      if (e != hipSuccess) { set_error("hipFuncSetAttribute(LDS %d B): %s", F6_LDS, hipGetErrorString(e)); return SPQ_ERR_LAUNCH; }
-      (void)hipFuncSetAttribute((const void*)gemm_fp6_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, F6_LDS);
-      (void)hipFuncSetAttribute((const void*)gemm_fp6_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, F6_LDS);
-    }
-    const int ntiles = q.tiles_m * q.tiles_n;
-    const unsigned cus3 = 3 * gemm_grid(1 << 30);
-    const unsigned grid6 = (unsigned)ntiles < cus3 ? (unsigned)ntiles : cus3;
-    if (a->ev_gemm_begin) (void)hipEventRecord((hipEvent_t)a->ev_gemm_begin, st);
-    if ((a->N & 3) != 0) gemm_fp6_kernel<0, true><<<grid6, 256, F6_LDS, st>>>(q);           // (fp6_validate: no GELU with a ragged N)
-    else if (a->epilogue == SPQ_EPILOGUE_GELU) gemm_fp6_kernel<1, false><<<grid6, 256, F6_LDS, st>>>(q);
-    else gemm_fp6_kernel<0, false><<<grid6, 256, F6_LDS, st>>>(q);
-    if (a->ev_gemm_end) (void)hipEventRecord((hipEvent_t)a->ev_gemm_end, st);
-    return check_launch("spq_linear_lora_fwd(gemm_fp6)");
-  }
-  if (i8nl) {
-    const PrepLayoutI8 P8 = make_prep_layout_i8(a->N, a->K, a->r, i8nl);
-    GemmI8Args q;
-    q.qx = reinterpret_cast<const signed char*>(x.qx); q.W = reinterpret_cast<const signed char*>(wp); q.plane_stride = (int64_t)P8.plane;
-    q.thi = x.thi; q.tlo = x.tlo;
-    q.Bhi = (const _Float16*)(wp + P8.off_bhi); q.Blo = (const _Float16*)(wp + P8.off_blo);
-    q.rowinv = x.rowinv; q.rowscale = a->w_rowscale; q.bscale = (const float*)(wp + P8.off_bscale); q.bias = a->bias; q.y = a->y;
-    q.M = (int)a->M; q.N = (int)a->N; q.Kp = (int)L.Kp; q.Rp = lora_up ? (int)L.Rp : 0;
-    q.tiles_m = (int)(L.Mp / GM); q.tiles_n = (int)(P8.Np / GN); q.epilogue = a->epilogue;
-    // 128-deep stages (whole cache lines, half as many stages: measured 50-53 us against 56-59 at the c_fc shape) whenever K
-    // allows; the 64-deep ring kernel otherwise
-    const bool k128 = (L.Kp % 128) == 0;
-    if (AttrOnce once(1); once.first) {
-      hipError_t e = hipFuncSetAttribute((const void*)gemm_i8_kernel<1, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, I8_LDS);
-      if (e != hipSuccess) { set_error("hipFuncSetAttribute(LDS %d B): %s", I8_LDS, hipGetErrorString(e)); return SPQ_ERR_LAUNCH; }
-      (void)hipFuncSetAttribute((const void*)gemm_i8_kernel<1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, I8_LDS);
-      (void)hipFuncSetAttribute((const void*)gemm_i8_k128_kernel<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, i8k_lds(1));
-      (void)hipFuncSetAttribute((const void*)gemm_i8_k128_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, i8k_lds(1));
-    }
-    const bool gelu8 = a->epilogue == SPQ_EPILOGUE_GELU;
-    if (a->ev_gemm_begin) (void)hipEventRecord((hipEvent_t)a->ev_gemm_begin, st);
-    if (k128) {
-      const int ntiles = 2 * q.tiles_m * q.tiles_n;
-      const unsigned cus2 = 2 * gemm_grid(1 << 30);
-      const unsigned g128 = (unsigned)ntiles < cus2 ? (unsigned)ntiles : cus2;
-      if (gelu8) gemm_i8_k128_kernel<1, 1><<<g128, 256, i8k_lds(1), st>>>(q);
-      else gemm_i8_k128_kernel<1, 0><<<g128, 256, i8k_lds(1), st>>>(q);
-    } else {
-      const unsigned grid8 = gemm_grid(q.tiles_m * q.tiles_n);
-      if (gelu8) gemm_i8_kernel<1, 0, 1><<<grid8, I8_THREADS, I8_LDS, st>>>(q);
-      else gemm_i8_kernel<1, 0, 0><<<grid8, I8_THREADS, I8_LDS, st>>>(q);
-    }
-    if (a->ev_gemm_end) (void)hipEventRecord((hipEvent_t)a->ev_gemm_end, st);
-    return check_launch("spq_linear_lora_fwd(gemm_i8)");
-  }
-  GemmF16Args g;
-  g.qx = x.qx; g.thi = x.thi; g.tlo = x.tlo;
-  g.Whi = (const _Float16*)(wp + P.off_whi); g.Wlo = (const _Float16*)(wp + P.off_wlo);
-  g.Bhi = (const _Float16*)(wp + P.off_bhi); g.Blo = (const _Float16*)(wp + P.off_blo);
-  g.rowinv = x.rowinv; g.rowscale = a->w_rowscale; g.bias = a->bias; g.y = a->y;
-  g.M = (int)a->M; g.N = (int)a->N; g.Kp = (int)L.Kp; g.Rp = lora_up ? (int)L.Rp : 0;
-  g.tiles_m = (int)(L.Mp / GM); g.tiles_n = (int)(P.Np / GN); g.dbg = nullptr;
-  g.xl = x.xl; g.xscale = a->x_limb_scale; g.a_limbs = x3 ? 2 : 1;
-  g.lv = (_Float16*)a->out_levels; g.lv_scale = a->out_scale; g.lv_ld = (int)a->out_levels_ld; g.lv_pc = a->out_scale_per_channel;
-  g.lv_qhi = 0.f;
-  g.lv_lo = (_Float16*)a->out_levels_lo; g.lv_zero = a->out_zero; g.lv_xscale = a->out_limb_scale;
-  g.lv_qtype = a->out_qtype; g.lv_sym = a->out_symmetric; g.lv_bits = a->out_bits;
-  if (a->out_levels) {
+  if (p.g_kind == G_T128 && a->out_levels) {
     const bool limbs_out = a->out_levels_lo != nullptr;
     const bool common = a->out_scale && (a->N % 64) == 0 && a->out_levels_ld >= a->N && (a->out_levels_ld % 4) == 0 && aligned16(a->out_levels) &&
                         aligned16(a->out_scale);
     const bool ok = limbs_out ? (common && a->out_zero && a->out_limb_scale && a->out_bits >= 1 && a->out_bits <= 24 && aligned16(a->out_levels_lo) &&
                                  aligned16(a->out_zero) && (a->out_qtype == SPQ_MINMAX || a->out_qtype == SPQ_LOG || a->out_qtype == SPQ_LOG_DIRECT))
                               : (common && a->out_bits >= 2 && a->out_bits <= 12);
-    if (!ok) {
-      set_error("spq_linear_lora_fwd: levels-out store needs out_scale, N %% 64 == 0, a 16-B aligned level matrix with row pitch >= N, and 2..12 "
-                "out_bits (levels) or out_zero + out_limb_scale + 1..24 out_bits (limbs) (got bits=%d N=%lld ld=%lld limbs=%d)", a->out_bits,
-                (long long)a->N, (long long)a->out_levels_ld, (int)limbs_out);
-      return SPQ_ERR_UNSUPPORTED;
-    }
-    if (!limbs_out) g.lv_qhi = (float)((1 << (a->out_bits - 1)) - 1);
+    if (!ok)
+      SPQ_REFUSE("spq_linear_lora_fwd: levels-out store needs out_scale, N %% 64 == 0, a 16-B aligned level matrix with row pitch >= N, and 2..12 "
+                 "out_bits (levels) or out_zero + out_limb_scale + 1..24 out_bits (limbs) (got bits=%d N=%lld ld=%lld limbs=%d)", a->out_bits,
+                 (long long)a->N, (long long)a->out_levels_ld, (int)limbs_out);
   }
-  if (AttrOnce once(3); once.first) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_f16x2_t128_kernel<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, T128_LDS);
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute(LDS %d B): %s", T128_LDS, hipGetErrorString(e)); return SPQ_ERR_LAUNCH; }
-#define SPQ_T128_ATTR(AL, EPI, LV) (void)hipFuncSetAttribute((const void*)gemm_f16x2_t128_kernel<AL, EPI, LV>, hipFuncAttributeMaxDynamicSharedMemorySize, T128_LDS)
-    SPQ_T128_ATTR(2, 0, 0); SPQ_T128_ATTR(1, 1, 0); SPQ_T128_ATTR(2, 1, 0);
-    SPQ_T128_ATTR(1, 0, 1); SPQ_T128_ATTR(2, 0, 1); SPQ_T128_ATTR(1, 1, 1); SPQ_T128_ATTR(2, 1, 1);
-    SPQ_T128_ATTR(1, 0, 2); SPQ_T128_ATTR(2, 0, 2); SPQ_T128_ATTR(1, 1, 2); SPQ_T128_ATTR(2, 1, 2);
-#undef SPQ_T128_ATTR
-    (void)hipFuncSetAttribute((const void*)gemm_f16x2_t128_kernel<1, 0, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T128_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_f16x2_t128_kernel<2, 0, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T128_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_f16x2_t128_kernel<1, 0, 0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T128_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_f16x2_t128_kernel<2, 0, 0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T128_LDS);
+  if (p.g_kind == G_T128 && (a->N & 3) != 0 && (a->epilogue == SPQ_EPILOGUE_GELU || a->out_levels))
+    SPQ_REFUSE("spq_linear_lora_fwd: the fused GELU / levels-out epilogues need N %% 4 == 0 (got N=%lld)", (long long)a->N);
+  const bool have_x = p.x_kind == X_NONE || (p.x_kind == X_STREAM_PREP ? kXStreamPrep.find(p.x_key) != nullptr : x_family(p.x_kind).find(p.x_key) != nullptr);
+  const bool have_g = p.g_kind == G_NONE || (p.g_kind == G_FP6 ? kGemmFp6.find(p.g_key) != nullptr
+                                             : p.g_kind == G_I8 ? kGemmI8.find(p.g_key) != nullptr : kGemmT128.find(p.g_key) != nullptr);
+  if (!have_x || !have_g) SPQ_REFUSE("spq_linear_lora_fwd: no kernel instantiated for this combination (activation %d/0x%x, contraction %d/0x%x)",
+                                     p.x_kind, p.x_key, p.g_kind, p.g_key);
+  return SPQ_OK;
+}
+#undef SPQ_REFUSE
+
+// ---- launch ----------------------------------------------------------------------------------------------------------
+static XPassArgs fill_xpass(const spq_fwd_args* a, const FwdPlan& p, const F16x2Layout& L) {
+  char* ws = (char*)a->workspace;
+  XPassArgs x;
+  x.zero_ptr = p.sk_zero_in_xpass ? (int*)(ws + L.off_skcnt) : nullptr; x.zero_n = p.sk_zero_in_xpass ? (int)(2 * p.sk_tiles) : 0;
+  x.x = a->x; x.sx = a->sx; x.zx = a->zx; x.aT = a->a_prep;
+  x.qx = (_Float16*)(ws + L.off_qx); x.thi = (_Float16*)(ws + L.off_thi); x.tlo = (_Float16*)(ws + L.off_tlo);
+  x.rowinv = (float*)(ws + L.off_rowinv);
+  x.M = (int)a->M; x.K = (int)a->K; x.r = (int)a->r; x.Kp = (int)L.Kp; x.Rp = (int)L.Rp;
+  x.x_pc = a->x_per_channel; x.bits = a->bits;
+  x.limbs = a->path == SPQ_PATH_F16X3; x.qtype = a->qtype; x.symmetric = a->symmetric;
+  if (x.limbs && !a->quantize_input) {   // identity quantizer: limbs of x itself; the scale loads read a valid dummy
+    x.bits = 32; x.qtype = SPQ_MINMAX; x.symmetric = 1; x.x_pc = 0; x.sx = a->x_limb_scale; x.zx = a->x_limb_scale;
   }
-  g.split = sk; g.sk_cnt = (int*)(ws + L.off_skcnt); g.sk_part = (float*)(ws + L.off_skpart);
-  if (sk > 1 && !sk_zeroed && hipMemsetAsync(g.sk_cnt, 0, (size_t)(2 * sk_nwg) * sizeof(int), st) != hipSuccess) {
+  x.xl = (_Float16*)(ws + L.off_xl); x.xscale = a->x_limb_scale;
+  x.t_out = (a->r > 0) ? a->t_out : nullptr;
+  x.lora_fq = (a->lora_on_fq_input && a->quantize_input) ? 1 : 0;
+  x.ln_w = a->ln_weight; x.ln_b = a->ln_bias; x.ln_eps = a->ln_eps;
+  x.a8 = a->path == SPQ_PATH_FP6 ? 4 : i8_limbs_of(a->path) ? 2 : 0;
+  x.a6 = (unsigned char*)(ws + L.off_qx); x.kb6 = (int)((a->K + 127) / 128);
+  return x;
+}
+
+// the activation launch.  LDS limits: panel <- streaming <- streaming + preparation, each use raises everything to its left too
+static int launch_xpass(const spq_fwd_args* a, const FwdPlan& p, const F16x2Layout& L, const PrepArgs& pa, hipStream_t st) {
+  const XPassArgs x = fill_xpass(a, p, L);
+  int rc = p.x_kind >= X_PANEL ? kXPanel.raise_lds() : SPQ_OK;
+  if (!rc && p.x_kind >= X_STREAM) rc = kXStream.raise_lds();
+  if (!rc && p.x_kind == X_STREAM_PREP) rc = kXStreamPrep.raise_lds();
+  if (rc) return rc;
+  if (p.x_kind == X_STREAM_PREP) kXStreamPrep.launch(p.x_key, p.x_grid, p.x_block, st, x, pa, (int)p.x_nx);
+  else x_family(p.x_kind).launch(p.x_key, p.x_grid, p.x_block, st, x);
+  return check_launch("spq_linear_lora_fwd(xpass)");
+}
+
+// the contraction launch itself, the profiling events immediately around it
+template <class... A>
+static int launch_contraction(const spq_fwd_args* a, const FwdPlan& p, hipStream_t st, const Family<A...>& f, const char* what, const A&... args) {
+  const int rc = f.raise_lds();
+  if (rc) return rc;
+  if (a->ev_gemm_begin) (void)hipEventRecord((hipEvent_t)a->ev_gemm_begin, st);
+  f.launch(p.g_key, p.g_grid, p.g_block, st, args...);
+  if (a->ev_gemm_end) (void)hipEventRecord((hipEvent_t)a->ev_gemm_end, st);
+  return check_launch(what);
+}
+
+static int launch_gemm_fp6(const spq_fwd_args* a, const FwdPlan& p, const F16x2Layout& L, hipStream_t st) {
+  char* ws = (char*)a->workspace;
+  const char* wp = (const char*)a->w_prep;
+  const PrepLayoutFp6 P6 = make_prep_layout_fp6(a->N, a->K, a->r);
+  GemmFp6Args q;
+  q.A6 = (unsigned char*)(ws + L.off_qx); q.W6 = (const unsigned char*)wp; q.plane_stride = (int64_t)P6.plane;
+  q.rowscale = a->w_rowscale; q.bfac = (const float*)(wp + P6.off_bfac); q.bias = a->bias; q.y = a->y;
+  q.M = (int)a->M; q.N = (int)a->N; q.KB = (int)P6.KB; q.tiles_m = (int)(L.Mp / 128); q.tiles_n = (int)(P6.Np / 128);
+  q.thi = (_Float16*)(ws + L.off_thi); q.tlo = (_Float16*)(ws + L.off_tlo);
+  q.Bhi = (const _Float16*)(wp + P6.off_bhi); q.Blo = (const _Float16*)(wp + P6.off_blo);
+  q.rowinv = (float*)(ws + L.off_rowinv); q.Rp = a->b_prep ? (int)L.Rp : 0;
+  return launch_contraction(a, p, st, kGemmFp6, "spq_linear_lora_fwd(gemm_fp6)", q);
+}
+
+static int launch_gemm_i8(const spq_fwd_args* a, const FwdPlan& p, const F16x2Layout& L, hipStream_t st) {
+  char* ws = (char*)a->workspace;
+  const char* wp = (const char*)a->w_prep;
+  const PrepLayoutI8 P8 = make_prep_layout_i8(a->N, a->K, a->r, i8_limbs_of(a->path));
+  GemmI8Args q;
+  q.qx = (const signed char*)(ws + L.off_qx); q.W = (const signed char*)wp; q.plane_stride = (int64_t)P8.plane;
+  q.thi = (_Float16*)(ws + L.off_thi); q.tlo = (_Float16*)(ws + L.off_tlo);
+  q.Bhi = (const _Float16*)(wp + P8.off_bhi); q.Blo = (const _Float16*)(wp + P8.off_blo);
+  q.rowinv = (float*)(ws + L.off_rowinv); q.rowscale = a->w_rowscale; q.bscale = (const float*)(wp + P8.off_bscale); q.bias = a->bias; q.y = a->y;
+  q.M = (int)a->M; q.N = (int)a->N; q.Kp = (int)L.Kp; q.Rp = a->b_prep ? (int)L.Rp : 0;
+  q.tiles_m = (int)(L.Mp / GM); q.tiles_n = (int)(P8.Np / GN); q.epilogue = a->epilogue;
+  return launch_contraction(a, p, st, kGemmI8, "spq_linear_lora_fwd(gemm_i8)", q);
+}
+
+static int launch_gemm_t128(const spq_fwd_args* a, const FwdPlan& p, const F16x2Layout& L, hipStream_t st) {
+  char* ws = (char*)a->workspace;
+  const char* wp = (const char*)a->w_prep;
+  const PrepLayout P = make_prep_layout(a->N, a->K, a->r);
+  GemmF16Args g;
+  g.qx = (_Float16*)(ws + L.off_qx); g.thi = (_Float16*)(ws + L.off_thi); g.tlo = (_Float16*)(ws + L.off_tlo);
+  g.Whi = (const _Float16*)(wp + P.off_whi); g.Wlo = (const _Float16*)(wp + P.off_wlo);
+  g.Bhi = (const _Float16*)(wp + P.off_bhi); g.Blo = (const _Float16*)(wp + P.off_blo);
+  g.rowinv = (float*)(ws + L.off_rowinv); g.rowscale = a->w_rowscale; g.bias = a->bias; g.y = a->y;
+  g.M = (int)a->M; g.N = (int)a->N; g.Kp = (int)L.Kp; g.Rp = a->b_prep ? (int)L.Rp : 0;
+  g.tiles_m = (int)(L.Mp / GM); g.tiles_n = (int)(P.Np / GN); g.dbg = nullptr;
+  g.xl = (_Float16*)(ws + L.off_xl); g.xscale = a->x_limb_scale; g.a_limbs = a->path == SPQ_PATH_F16X3 ? 2 : 1;
+  g.lv = (_Float16*)a->out_levels; g.lv_scale = a->out_scale; g.lv_ld = (int)a->out_levels_ld; g.lv_pc = a->out_scale_per_channel;
+  g.lv_qhi = (a->out_levels && !a->out_levels_lo) ? (float)((1 << (a->out_bits - 1)) - 1) : 0.f;
+  g.lv_lo = (_Float16*)a->out_levels_lo; g.lv_zero = a->out_zero; g.lv_xscale = a->out_limb_scale;
+  g.lv_qtype = a->out_qtype; g.lv_sym = a->out_symmetric; g.lv_bits = a->out_bits;
+  g.split = p.sk; g.sk_cnt = (int*)(ws + L.off_skcnt); g.sk_part = (float*)(ws + L.off_skpart);
+  if (p.sk > 1 && !p.sk_zero_in_xpass && hipMemsetAsync(g.sk_cnt, 0, (size_t)(2 * p.sk_tiles) * sizeof(int), st) != hipSuccess) {
     set_error("spq_linear_lora_fwd: hipMemsetAsync(split-K counters) failed"); (void)hipGetLastError(); return SPQ_ERR_LAUNCH;
   }
-  if (a->ev_gemm_begin) (void)hipEventRecord((hipEvent_t)a->ev_gemm_begin, st);
-  // ONE contraction kernel for every shape (128 x 128 tiles, three workgroups per CU); the 256 x 128 persistent kernels of round 1
-  // live in tools/variants/gemm_256x128.h (measured slower at every shape of SURVEY 8(d): config 3 1.466 -> 1.356 ms, config 5
-  // 27.8 -> 27.4 ms)
-  const bool gelu = a->epilogue == SPQ_EPILOGUE_GELU;
-  const bool ragged = (a->N & 3) != 0;                     // rows of y not 16-B aligned: the scalar-store instantiation (plain epilogue)
-  if (ragged && (gelu || g.lv)) { set_error("spq_linear_lora_fwd: the fused GELU / levels-out epilogues need N %% 4 == 0 (got N=%lld)", (long long)a->N); return SPQ_ERR_UNSUPPORTED; }
-  const int ntiles = 2 * g.tiles_m * g.tiles_n * sk;
-  const unsigned cus3 = (sk > 1 ? 2 : 1) * T128_WGS * gemm_grid(1 << 30);    // split-K: one unit per workgroup
-  const unsigned grid128 = (unsigned)ntiles < cus3 ? (unsigned)ntiles : cus3;
-#define SPQ_T128_LAUNCH(AL, EPI, LV) gemm_f16x2_t128_kernel<AL, EPI, LV><<<grid128, 256, T128_LDS, st>>>(g)
-#define SPQ_T128_PICK(LV) do { if (x3 && gelu) SPQ_T128_LAUNCH(2, 1, LV); else if (x3) SPQ_T128_LAUNCH(2, 0, LV); \
-                               else if (gelu) SPQ_T128_LAUNCH(1, 1, LV); else SPQ_T128_LAUNCH(1, 0, LV); } while (0)
-  if (g.lv && g.lv_lo) SPQ_T128_PICK(2);
-  else if (g.lv) SPQ_T128_PICK(1);
-  else if (ragged) { if (x3) gemm_f16x2_t128_kernel<2, 0, 0, false, true><<<grid128, 256, T128_LDS, st>>>(g); else gemm_f16x2_t128_kernel<1, 0, 0, false, true><<<grid128, 256, T128_LDS, st>>>(g); }
-  else if (sk > 1) { if (x3) gemm_f16x2_t128_kernel<2, 0, 0, true><<<grid128, 256, T128_LDS, st>>>(g); else gemm_f16x2_t128_kernel<1, 0, 0, true><<<grid128, 256, T128_LDS, st>>>(g); }
-  else SPQ_T128_PICK(0);
-#undef SPQ_T128_PICK
-#undef SPQ_T128_LAUNCH
-  if (a->ev_gemm_end) (void)hipEventRecord((hipEvent_t)a->ev_gemm_end, st);
-  return check_launch("spq_linear_lora_fwd(gemm_t128)");
+  return launch_contraction(a, p, st, kGemmT128, "spq_linear_lora_fwd(gemm_t128)", g);
+}
+
+int fwd_f16x2(const spq_fwd_args* a, hipStream_t st) {
+  FwdPlan p;
+  PrepArgs pa;
+  int rc = fwd_validate(a, g_switches, p, pa);
+  if (rc) return rc;
+  const F16x2Layout L = make_layout(a->M, a->K, a->r, a->path == SPQ_PATH_FP6 ? 0 : a->N, a->path == SPQ_PATH_F16X3 ? 2 : i8_limbs_of(a->path) ? -1 : 1);
+  if (p.at_blocks) {
+    fq_transpose_kernel<<<(unsigned)p.at_blocks, 256, 0, st>>>(pa);
+    if ((rc = check_launch("spq_linear_lora_fwd(FQ(A)^T)"))) return rc;
+  }
+  if (p.prep_launch && (rc = spq_prepare_f16x2_args(a->prepare, (spq_stream_t)st))) return rc;
+  if (p.x_kind != X_NONE && (rc = launch_xpass(a, p, L, pa, st))) return rc;
+  switch (p.g_kind) {
+    case G_FP6: return launch_gemm_fp6(a, p, L, st);
+    case G_I8: return launch_gemm_i8(a, p, L, st);
+    case G_T128: return launch_gemm_t128(a, p, L, st);
+  }
+  return SPQ_OK;
 }
 
 }  // namespace spq
@@ -2213,8 +2247,8 @@ extern "C" size_t spq_prep_bytes(int64_t N, int64_t K, int64_t r, int path) {
 }
 
 namespace spq {
-// validation + PrepArgs of one spq_prepare_args; at_blocks = FQ(A)^T tiles, wave_ok = the one-wave-per-row kernel applies
-int prepare_fill(const spq_prepare_args* q, PrepArgs& a, int& at_blocks, bool& wave_ok) {
+// validation + PrepArgs of one spq_prepare_args
+int prepare_fill(const spq_prepare_args* q, PrepArgs& a) {
   SPQ_REQUIRE(q, "spq_prepare_f16x2: null args");
   SPQ_REQUIRE(q->W && q->sw && q->zw && q->sx && q->w_prep && q->w_rowscale, "spq_prepare_f16x2: null pointer");
   SPQ_REQUIRE(q->N > 0 && q->K > 0 && q->r >= 0, "spq_prepare_f16x2: bad shape");
@@ -2259,10 +2293,8 @@ int prepare_fill(const spq_prepare_args* q, PrepArgs& a, int& at_blocks, bool& w
   a.x_pc = q->x_per_channel; a.scaling = q->scaling;
   a.A = q->A; a.sa = q->sa; a.za = q->za; a.aT = q->a_prep;
   a.a_pc = q->a_per_channel; a.a_bits = q->a_bits; a.a_qtype = q->a_qtype; a.a_sym = q->a_symmetric;
-  at_blocks = (r > 0 && q->A) ? (int)(((r + 31) / 32) * ((K + 31) / 32)) : 0;   // A == NULL: FQ(A)^T is made elsewhere
-  wave_ok = (K % 4 == 0) && K <= 4 * 64 * PREP_MAXI && aligned16(q->W) && (!q->x_per_channel || aligned16(q->sx)) && r <= 128;
-  a.row_blocks = wave_ok ? (int)(P.Np / 4) : (int)P.Np;
-  if (fp6) { wave_ok = false; a.row_blocks = (int)(P6.Np / 32); }
+  const bool wave_ok = prep_wave_ok(q);
+  a.row_blocks = fp6 ? (int)(P6.Np / 32) : wave_ok ? (int)(P.Np / 4) : (int)P.Np;
   if (nl && !wave_ok) {
     set_error("spq_prepare_f16x2: the int8 operand paths need K %% 4 == 0, K <= %d and 16-byte aligned W / sx", 4 * 64 * PREP_MAXI);
     return SPQ_ERR_UNSUPPORTED;
@@ -2273,10 +2305,10 @@ int prepare_fill(const spq_prepare_args* q, PrepArgs& a, int& at_blocks, bool& w
 
 extern "C" int spq_prepare_f16x2_args(const spq_prepare_args* q, spq_stream_t stream) {
   PrepArgs a;
-  int at_blocks = 0;
-  bool wave_ok = false;
-  const int rc = prepare_fill(q, a, at_blocks, wave_ok);
+  const int rc = prepare_fill(q, a);
   if (rc) return rc;
+  const int at_blocks = prep_at_blocks(q);
+  const bool wave_ok = prep_wave_ok(q);
   const unsigned grid = (unsigned)(a.row_blocks + at_blocks);
   const bool short_rows = q->K <= 4 * 64 * 4;
   if (q->path == SPQ_PATH_FP6) {
