@@ -159,6 +159,33 @@ int spq_layernorm(const float* x, int64_t rows, int64_t cols, const float* weigh
                   spq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * SwitchableLayerNorm under autograd: the forward that keeps the row statistics, and the backward torch's autograd derives
+ * from switchable_batchnorm.py:102-109 (the reference has no hand-written backward; it records the eight ops of the formula).
+ *
+ * spq_layernorm_fwd_stats: spq_layernorm (same arithmetic, bit-identical `out`) that also writes mean[rows] and
+ *   den[rows] = sqrt(var + eps), the two values the backward needs besides x.
+ * spq_layernorm_bwd: with xh = (x - mean) / den (recomputed, the forward's own two operations) and gw = g * weight,
+ *     dx      = ((gw - mean_k(gw)) - xh * mean_k(gw * xh)) / den      [rows, cols]
+ *     dweight = sum_rows g * xh,   dbias = sum_rows g                 [cols]
+ *   Any of dx / dweight / dbias may be NULL (not all three): that part of the work, and the loads only it needs, are skipped;
+ *   weight may be NULL when dx is, x / mean / den when only dbias is asked for, workspace when neither sum is.
+ *   One read of g, one of x, one write of dx for cols <= 2048; wider rows read g and x a second time for the column sums.
+ *   The column sums are a fixed tree over S = min(512, ceil(rows / 16)) slabs of consecutive rows, slab s = rows
+ *   [s rows / S, (s + 1) rows / S) -- a function of rows only, no atomics -- so dweight / dbias are bit-identical run to run, and dx of a row does
+ *   not depend on the other rows of the call.  NaN / Inf propagate as in torch.
+ *   workspace: spq_layernorm_bwd_workspace_bytes(rows, cols) = S * 2 * cols * 4 bytes, 16-byte aligned (0 for a shape
+ *   the kernels do not serve).
+ * Same domain as spq_layernorm: cols % 4 == 0, cols <= 8192, 16-byte aligned tensors; SPQ_ERR_UNSUPPORTED otherwise,
+ * SPQ_ERR_WORKSPACE for a short or misaligned workspace, both before anything is enqueued.
+ * ------------------------------------------------------------------------------------------------- */
+int spq_layernorm_fwd_stats(const float* x, int64_t rows, int64_t cols, const float* weight, const float* bias, float eps,
+                            float* out, float* mean, float* den, spq_stream_t stream);
+size_t spq_layernorm_bwd_workspace_bytes(int64_t rows, int64_t cols);
+int spq_layernorm_bwd(const float* g, const float* x, const float* mean, const float* den, const float* weight, int64_t rows,
+                      int64_t cols, float* dx, float* dweight, float* dbias, void* workspace, size_t workspace_bytes,
+                      spq_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * The path's only exchange step: before finish_calibration every rank merges the running
  * statistics of its input quantizers (quantization.py:202-207 across ranks) with ONE in-place
  * all-reduce(MAX) over the flat fp32 buffer [-min_0 .. | max_0 ..] -- ncclAllReduce(ncclFloat, ncclMax) of

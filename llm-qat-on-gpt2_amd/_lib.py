@@ -71,6 +71,9 @@ SIGNATURES = {
     "spq_prepare_cpt": (_int, [_p, _i64, _i64, _p, _p, _int, _int, _int, _int, _p, _p, _i64, _p, _p, _int, _int, _int, _int, _f,
                                 _p, _int, _int, _p, _sz, _p, _p, _p, _p, _p, _p]),
     "spq_layernorm": (_int, [_p, _i64, _i64, _p, _p, _f, _p, _p]),
+    "spq_layernorm_fwd_stats": (_int, [_p, _i64, _i64, _p, _p, _f, _p, _p, _p, _p]),
+    "spq_layernorm_bwd_workspace_bytes": (_sz, [_i64, _i64]),
+    "spq_layernorm_bwd": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _sz, _p]),
     "spq_debug_reload_switches": (_int, []),
     "spq_debug_split_k": (_int, [_i64, _i64, _i64, _i64, _int]),
     "spq_version": (_int, []),

@@ -4,10 +4,12 @@ c_proj applied inside c_fc's contraction store.  Drop-ins for the reference's cl
 (part1_switchable_precision/switchable_batchnorm.py:6-109, models_sp.py:76-128); the reference's own ``SPBlock`` /
 ``SPAttention`` / ``SPModel`` assemble them unchanged (rebind the two names in models_sp).
 """
+import os
 from typing import List, Union
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .sp_linear import SPLinearWithLoRA
@@ -50,8 +52,60 @@ class _LayerNormCompat:
         return _ParamView(self.parent.biases[self.key])
 
 
+# SPQ_LN_AUTOGRAD=0: SwitchableLayerNorm under autograd takes the composed formula on stock torch ops instead of the HIP
+# forward / backward pair (the default of ``SwitchableLayerNorm.fuse_backward``); read once, at import
+_LN_AUTOGRAD = os.environ.get('SPQ_LN_AUTOGRAD', '1')[:1] != '0'
+
+
+class _LayerNormFunction(torch.autograd.Function):
+    """``spq_layernorm_fwd_stats`` with the backward torch's autograd derives from switchable_batchnorm.py:102-109
+    (``spq_layernorm_bwd``).  Saved: x, weight and the row statistics mean / den = sqrt(var + eps) -- the normalised tensor is
+    recomputed.  fp32 only; the kernels are opaque to autocast, so an fp32 input stays fp32 under it."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        cols = weight.numel()
+        xc = x.contiguous()
+        rows = xc.numel() // cols
+        out = torch.empty_like(xc)
+        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+        den = torch.empty(rows, dtype=torch.float32, device=x.device)
+        with _lib.on_device(x.device):
+            rc = _lib.load().spq_layernorm_fwd_stats(xc.data_ptr(), rows, cols, weight.data_ptr(), bias.data_ptr(), float(eps),
+                                                     out.data_ptr(), mean.data_ptr(), den.data_ptr(), _lib.stream_ptr(x.device))
+        _lib.check(rc, "spq_layernorm_fwd_stats")
+        ctx.save_for_backward(xc, weight, mean, den)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, weight, mean, den = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        if not (need_x or need_w or need_b):
+            return None, None, None, None
+        cols = weight.numel()
+        rows = x.numel() // cols
+        g = g.contiguous().float()
+        lib = _lib.load()
+        dx = torch.empty_like(x) if need_x else None
+        dw = torch.empty_like(weight) if need_w else None
+        db = torch.empty_like(weight) if need_b else None
+        with _lib.on_device(x.device):
+            st = _lib.stream_ptr(x.device)
+            ws = _lib.workspace(x.device, lib.spq_layernorm_bwd_workspace_bytes(rows, cols), st) if (need_w or need_b) else None
+            rc = lib.spq_layernorm_bwd(g.data_ptr(), x.data_ptr(), mean.data_ptr(), den.data_ptr(), weight.data_ptr(), rows, cols,
+                                       _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), 0 if ws is None else ws.numel(), st)
+        _lib.check(rc, "spq_layernorm_bwd")
+        return dx, dw, db, None
+
+
 class SwitchableLayerNorm(nn.Module):
-    """One weight/bias pair per precision over a shared normalisation (switchable_batchnorm.py:6-109)."""
+    """One weight/bias pair per precision over a shared normalisation (switchable_batchnorm.py:6-109).  On the GPU (fp32, 1-D
+    ``normalized_shape``) it is one HIP pass; with a gradient needed, the HIP forward / backward pair of ``_LayerNormFunction``
+    (``fuse_backward = False``, or ``SPQ_LN_AUTOGRAD=0``, restores the composed formula under autograd)."""
+
+    fuse_backward = _LN_AUTOGRAD
 
     def __init__(self, normalized_shape: Union[int, List[int], torch.Size], precision_levels: List[int] = [6, 8, 16, 32],
                  eps: float = 1e-5):
@@ -87,11 +141,13 @@ class SwitchableLayerNorm(nn.Module):
         bias = self.biases[str(self.current_precision)]
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or bias.requires_grad)
         cols = self.normalized_shape[0]
-        fused = (x.is_cuda and not needs_grad and len(self.normalized_shape) == 1 and x.dtype == torch.float32
-                 and cols % 4 == 0 and cols <= 8192 and x.numel() > 0)
+        fused = (x.is_cuda and len(self.normalized_shape) == 1 and x.dtype == torch.float32
+                 and cols % 4 == 0 and cols <= 8192 and x.numel() > 0 and (not needs_grad or self.fuse_backward))
         if not fused:
             return self._composed(x, weight, bias)
         _lib.check_device(x.device)
+        if needs_grad:
+            return _LayerNormFunction.apply(x, weight, bias, self.eps)
         xc = x.contiguous()
         out = torch.empty_like(xc)
         with torch.cuda.device(x.device):

@@ -200,10 +200,12 @@ __global__ __launch_bounds__(256) void stats_merge_kernel(const float* __restric
 
 // SwitchableLayerNorm.forward (switchable_batchnorm.py:102-109).  One wave per row; the row lives in registers (NV float4 per
 // lane), statistics are two-pass (mean, then mean of squared deviations) like the reference's x.mean / x.var(unbiased=False).
-template <int NV>
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int64_t rows, int cols,
-                                                        const float* __restrict__ w, const float* __restrict__ b, float eps,
-                                                        float* __restrict__ out) {
+// ln_forward_row is the body of both forward kernels: STATS additionally keeps the row's mean and den = sqrt(var + eps) for the
+// backward, everything else is the same code, so both kernels write the same bits.
+template <int NV, bool STATS>
+__device__ __forceinline__ void ln_forward_row(const float* __restrict__ x, int64_t rows, int cols, const float* __restrict__ w,
+                                               const float* __restrict__ b, float eps, float* __restrict__ out,
+                                               float* __restrict__ mean_out, float* __restrict__ den_out) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -212,6 +214,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   float4 v[NV];
   float mean, den;
   ln_row_stats<NV>(xr, cols, eps, lane, v, mean, den);
+  if (STATS && lane == 0) { mean_out[row] = mean; den_out[row] = den; }
   float4 wvs[NV], bvs[NV];                                   // weight / bias pieces: all loads before the arithmetic (see ln_row_load)
   const int last = (cols >> 2) - 1;
 #pragma unroll
@@ -230,6 +233,212 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       *reinterpret_cast<float4*>(orow + c) = o;
     }
   }
+}
+template <int NV>
+__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int64_t rows, int cols,
+                                                        const float* __restrict__ w, const float* __restrict__ b, float eps,
+                                                        float* __restrict__ out) {
+  ln_forward_row<NV, false>(x, rows, cols, w, b, eps, out, nullptr, nullptr);
+}
+template <int NV>
+__global__ __launch_bounds__(256) void layernorm_stats_kernel(const float* __restrict__ x, int64_t rows, int cols,
+                                                              const float* __restrict__ w, const float* __restrict__ b, float eps,
+                                                              float* __restrict__ out, float* __restrict__ mean_out,
+                                                              float* __restrict__ den_out) {
+  ln_forward_row<NV, true>(x, rows, cols, w, b, eps, out, mean_out, den_out);
+}
+
+// =================================================================================================
+// SwitchableLayerNorm backward: torch's autograd of weight * ((x - mean) / sqrt(var + eps)) + bias (switchable_batchnorm.py:102-109).
+// With xh = (x - mean) / den (the forward's own two operations on the saved mean / den) and gw = g * weight:
+//   dx      = ((gw - mean_k(gw)) - xh * mean_k(gw * xh)) / den        per row
+//   dweight = sum_rows g * xh,   dbias = sum_rows g                   per column
+// The column sums are a fixed tree that depends on (rows, cols) only: rows are cut into S = ln_bwd_slabs(rows) slabs of
+// consecutive rows, slab s = rows [s rows / S, (s + 1) rows / S) (integer division: sizes differ by one at most); inside a slab row-lane t (a wave of the row kernel, a quarter of the column kernel)
+// adds rows t, t + 4, ... in order, the four row-lanes combine as ((t0 + t1) + t2) + t3, and ln_bwd_merge_kernel adds the
+// slab partials with sixteen interleaved chains combined in order.  No atomics, nothing depends on the CU count.
+// =================================================================================================
+constexpr int kLnBwdMaxSlabs = 512;       // partial traffic S * cols * 8 B: 4 % of the 12 B / element at 8192 rows
+constexpr int kLnBwdMinSlabRows = 16;     // about four rows per wave at least, so the weight / accumulator set-up is amortised
+
+__device__ __forceinline__ float4 ln_xhat(float4 v, float mean, float den) {
+  return make_float4((v.x - mean) / den, (v.y - mean) / den, (v.z - mean) / den, (v.w - mean) / den);
+}
+__device__ __forceinline__ void f4_add(float4& a, const float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+__device__ __forceinline__ void f4_add_mul(float4& a, const float4 g, const float4 h) {
+  a.x += g.x * h.x; a.y += g.y * h.y; a.z += g.z * h.z; a.w += g.w * h.w;
+}
+
+// Row form: one workgroup per slab, one wave per row at a time, g and x of the row in registers (NV float4 per lane each, all
+// loads issued before the arithmetic).  DX: write dx.  ACC = 2: every lane also accumulates g * xh and g of its own columns over
+// the slab's rows; ACC = 1: g only (dbias alone -- with !DX the x row is then not loaded at all); ACC = 0: neither (wide rows,
+// whose accumulators do not fit the register file: ln_bwd_cols_kernel).  part[slab][2][cols] = {dweight partial, dbias partial}.
+template <int NV, bool DX, int ACC>
+__global__ __launch_bounds__(256) void ln_bwd_rows_kernel(const float* __restrict__ g, const float* __restrict__ x,
+                                                          const float* __restrict__ mean, const float* __restrict__ den,
+                                                          const float* __restrict__ w, int64_t rows, int cols, int64_t S,
+                                                          float* __restrict__ dx, float* __restrict__ part) {
+  constexpr bool NEED_X = DX || ACC == 2;
+  constexpr bool KEEP_W = DX && NV <= 8;                    // wider rows re-read the (cache-resident) weight piece by piece
+  constexpr int NA = ACC ? NV : 1, NW = KEEP_W ? NV : 1;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int last = (cols >> 2) - 1;
+  const int64_t r0 = (int64_t)blockIdx.x * rows / S, r1 = ((int64_t)blockIdx.x + 1) * rows / S;
+  float4 wreg[NW], aw[NA], ab[NA];
+  if constexpr (KEEP_W) ln_row_load<NW>(w, cols, lane, wreg);
+#pragma unroll
+  for (int i = 0; i < NA; ++i) { aw[i] = make_float4(0.f, 0.f, 0.f, 0.f); ab[i] = aw[i]; }
+  for (int64_t row = r0 + wv; row < r1; row += 4) {
+    float4 gv[NV], xv[NEED_X ? NV : 1];
+    ln_row_load<NV>(g + row * cols, cols, lane, gv);
+    float m = 0.f, d = 1.f;
+    if constexpr (NEED_X) {
+      ln_row_load<NV>(x + row * cols, cols, lane, xv);
+      m = mean[row]; d = den[row];
+#pragma unroll
+      for (int i = 0; i < NV; ++i) xv[i] = ln_xhat(xv[i], m, d);
+    }
+    if constexpr (ACC != 0) {                               // lanes past the row's end accumulate a copy of its last piece: never stored
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        if constexpr (ACC == 2) f4_add_mul(aw[i], gv[i], xv[i]);
+        f4_add(ab[i], gv[i]);
+      }
+    }
+    if constexpr (DX) {
+      float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        float4 wvv;
+        if constexpr (KEEP_W) wvv = wreg[i]; else wvv = *reinterpret_cast<const float4*>(w + 4 * min(i * 64 + lane, last));
+        gv[i].x *= wvv.x; gv[i].y *= wvv.y; gv[i].z *= wvv.z; gv[i].w *= wvv.w;
+        if ((i * 64 + lane) * 4 < cols) {
+          s1 += (gv[i].x + gv[i].y) + (gv[i].z + gv[i].w);
+          s2 += (gv[i].x * xv[i].x + gv[i].y * xv[i].y) + (gv[i].z * xv[i].z + gv[i].w * xv[i].w);
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
+      const float m1 = s1 / (float)cols, m2 = s2 / (float)cols;
+      float* orow = dx + row * cols;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int c = (i * 64 + lane) * 4;
+        if (c < cols) {
+          float4 o;
+          o.x = ((gv[i].x - m1) - xv[i].x * m2) / d; o.y = ((gv[i].y - m1) - xv[i].y * m2) / d;
+          o.z = ((gv[i].z - m1) - xv[i].z * m2) / d; o.w = ((gv[i].w - m1) - xv[i].w * m2) / d;
+          *reinterpret_cast<float4*>(orow + c) = o;
+        }
+      }
+    }
+  }
+  if constexpr (ACC != 0) {
+    __shared__ float4 s_acc[3][ACC][NA * 64];               // waves 1..3 park their sums, wave 0 adds them in wave order
+    if (wv) {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        if constexpr (ACC == 2) s_acc[wv - 1][ACC - 1][i * 64 + lane] = aw[i];
+        s_acc[wv - 1][0][i * 64 + lane] = ab[i];
+      }
+    }
+    __syncthreads();
+    if (wv) return;
+    float* pw = part + (int64_t)blockIdx.x * 2 * cols;
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int c = (i * 64 + lane) * 4;
+      if (c < cols) {
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+          if constexpr (ACC == 2) f4_add(aw[i], s_acc[t][ACC - 1][i * 64 + lane]);
+          f4_add(ab[i], s_acc[t][0][i * 64 + lane]);
+        }
+        if constexpr (ACC == 2) *reinterpret_cast<float4*>(pw + c) = aw[i];
+        *reinterpret_cast<float4*>(pw + cols + c) = ab[i];
+      }
+    }
+  }
+}
+
+// Column form of the same sums, for rows too wide for register accumulators (and nothing else: the two forms add in the same
+// order but are never mixed within one cols).  grid = (ceil(cols / 256), S); block = 64 column lanes (one float4 each) x 4 row
+// lanes.  DW = false: dbias alone, x is not read.
+template <bool DW>
+__global__ __launch_bounds__(256) void ln_bwd_cols_kernel(const float* __restrict__ g, const float* __restrict__ x,
+                                                          const float* __restrict__ mean, const float* __restrict__ den,
+                                                          int64_t rows, int cols, int64_t S, float* __restrict__ part) {
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int c = (blockIdx.x * 64 + tx) * 4;
+  const int64_t r0 = (int64_t)blockIdx.y * rows / S, r1 = ((int64_t)blockIdx.y + 1) * rows / S;
+  float4 aw = make_float4(0.f, 0.f, 0.f, 0.f), ab = aw;
+  if (c < cols) {
+    int64_t r = r0 + ty;
+    for (; r + 12 < r1; r += 16) {                          // four independent 16-B loads per operand in flight per lane
+      float4 gv[4], xv[4];
+      float m[4], d[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        gv[u] = *reinterpret_cast<const float4*>(g + (r + 4 * u) * cols + c);
+        if (DW) { xv[u] = *reinterpret_cast<const float4*>(x + (r + 4 * u) * cols + c); m[u] = mean[r + 4 * u]; d[u] = den[r + 4 * u]; }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (DW) f4_add_mul(aw, gv[u], ln_xhat(xv[u], m[u], d[u]));
+        f4_add(ab, gv[u]);
+      }
+    }
+    for (; r < r1; r += 4) {
+      const float4 gv = *reinterpret_cast<const float4*>(g + r * cols + c);
+      if (DW) f4_add_mul(aw, gv, ln_xhat(*reinterpret_cast<const float4*>(x + r * cols + c), mean[r], den[r]));
+      f4_add(ab, gv);
+    }
+  }
+  __shared__ float4 s_acc[3][2][64];
+  if (ty) { s_acc[ty - 1][0][tx] = ab; if (DW) s_acc[ty - 1][1][tx] = aw; }
+  __syncthreads();
+  if (ty || c >= cols) return;
+#pragma unroll
+  for (int t = 0; t < 3; ++t) { f4_add(ab, s_acc[t][0][tx]); if (DW) f4_add(aw, s_acc[t][1][tx]); }
+  float* pw = part + (int64_t)blockIdx.y * 2 * cols;
+  if (DW) *reinterpret_cast<float4*>(pw + c) = aw;
+  *reinterpret_cast<float4*>(pw + cols + c) = ab;
+}
+
+// part[S][2][cols] -> dweight / dbias (either may be null).  64 consecutive columns per workgroup; wave t of sixteen adds slabs
+// t, t + 16, ... in order (eight loads in flight per output), then wave 0 adds the sixteen sums in wave order.
+__global__ __launch_bounds__(1024) void ln_bwd_merge_kernel(const float* __restrict__ part, int64_t S, int cols,
+                                                            float* __restrict__ dweight, float* __restrict__ dbias) {
+  __shared__ float s_w[16][64], s_b[16][64];
+  const int cl = threadIdx.x & 63, t = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + cl;
+  float sw = 0.f, sb = 0.f;
+  if (c < cols) {
+    int64_t sl = t;
+    for (; sl + 7 * 16 < S; sl += 8 * 16) {
+      float pw[8], pb[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const float* p = part + (sl + 16 * u) * 2 * cols + c;
+        if (dweight) pw[u] = p[0];
+        if (dbias) pb[u] = p[cols];
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { if (dweight) sw += pw[u]; if (dbias) sb += pb[u]; }
+    }
+    for (; sl < S; sl += 16) {
+      const float* p = part + sl * 2 * cols + c;
+      if (dweight) sw += p[0];
+      if (dbias) sb += p[cols];
+    }
+  }
+  s_w[t][cl] = sw; s_b[t][cl] = sb;
+  __syncthreads();
+  if (t || c >= cols) return;
+#pragma unroll
+  for (int u = 1; u < 16; ++u) { sw += s_w[u][cl]; sb += s_b[u][cl]; }
+  if (dweight) dweight[c] = sw;
+  if (dbias) dbias[c] = sb;
 }
 
 // {2^G, 2^-G} with max|x| * 2^G in [2^13, 2^14): the scale of the two-fp16-limb operand of an un-quantised tensor
@@ -500,6 +709,93 @@ extern "C" int spq_layernorm(const float* x, int64_t rows, int64_t cols, const f
   else if (nv <= 16) layernorm_kernel<16><<<grid, 256, 0, st>>>(x, rows, (int)cols, weight, bias, eps, out);
   else layernorm_kernel<32><<<grid, 256, 0, st>>>(x, rows, (int)cols, weight, bias, eps, out);
   return check_launch("spq_layernorm");
+}
+
+// the slab cut of the LayerNorm backward (see ln_bwd_rows_kernel): a function of rows only
+static inline int64_t ln_bwd_slabs(int64_t rows) { return std::min<int64_t>(kLnBwdMaxSlabs, ceil_div64(rows, kLnBwdMinSlabRows)); }
+// the checks spq_layernorm, spq_layernorm_fwd_stats and spq_layernorm_bwd share
+static inline bool ln_cols_ok(int64_t cols) { return cols > 0 && cols % 4 == 0 && cols <= 8192; }
+
+extern "C" int spq_layernorm_fwd_stats(const float* x, int64_t rows, int64_t cols, const float* weight, const float* bias,
+                                       float eps, float* out, float* mean, float* den, spq_stream_t stream) {
+  SPQ_REQUIRE(x && weight && bias && out && mean && den, "spq_layernorm_fwd_stats: null pointer");
+  SPQ_REQUIRE(rows > 0 && cols > 0, "spq_layernorm_fwd_stats: empty tensor");
+  if (!ln_cols_ok(cols) || !aligned16(x) || !aligned16(out) || !aligned16(weight) || !aligned16(bias)) {
+    set_error("spq_layernorm_fwd_stats: needs cols %% 4 == 0, cols <= 8192 and 16-byte aligned tensors (cols = %lld)", (long long)cols);
+    return SPQ_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = (unsigned)ceil_div64(rows, 4);
+  const int nv = (int)ceil_div64(cols, 256);
+  if (nv <= 2) layernorm_stats_kernel<2><<<grid, 256, 0, st>>>(x, rows, (int)cols, weight, bias, eps, out, mean, den);
+  else if (nv <= 4) layernorm_stats_kernel<4><<<grid, 256, 0, st>>>(x, rows, (int)cols, weight, bias, eps, out, mean, den);
+  else if (nv <= 8) layernorm_stats_kernel<8><<<grid, 256, 0, st>>>(x, rows, (int)cols, weight, bias, eps, out, mean, den);
+  else if (nv <= 16) layernorm_stats_kernel<16><<<grid, 256, 0, st>>>(x, rows, (int)cols, weight, bias, eps, out, mean, den);
+  else layernorm_stats_kernel<32><<<grid, 256, 0, st>>>(x, rows, (int)cols, weight, bias, eps, out, mean, den);
+  return check_launch("spq_layernorm_fwd_stats");
+}
+
+extern "C" size_t spq_layernorm_bwd_workspace_bytes(int64_t rows, int64_t cols) {
+  if (rows <= 0 || !ln_cols_ok(cols)) return 0;
+  return (size_t)ln_bwd_slabs(rows) * 2 * (size_t)cols * sizeof(float);
+}
+
+template <int NV>
+static void ln_bwd_rows_launch(bool want_dx, int acc, unsigned grid, hipStream_t st, const float* g, const float* x,
+                               const float* mean, const float* den, const float* w, int64_t rows, int cols, int64_t S,
+                               float* dx, float* part) {
+#define SPQ_LN_BWD(DX, ACC) ln_bwd_rows_kernel<NV, DX, ACC><<<grid, 256, 0, st>>>(g, x, mean, den, w, rows, cols, S, dx, part)
+  if constexpr (NV <= 8) {
+    if (want_dx) { if (acc == 2) SPQ_LN_BWD(true, 2); else if (acc == 1) SPQ_LN_BWD(true, 1); else SPQ_LN_BWD(true, 0); }
+    else if (acc == 2) SPQ_LN_BWD(false, 2);
+    else SPQ_LN_BWD(false, 1);
+  } else {
+    SPQ_LN_BWD(true, 0);                                    // wide rows: dx here, the column sums in ln_bwd_cols_kernel
+  }
+#undef SPQ_LN_BWD
+}
+
+extern "C" int spq_layernorm_bwd(const float* g, const float* x, const float* mean, const float* den, const float* weight,
+                                 int64_t rows, int64_t cols, float* dx, float* dweight, float* dbias, void* workspace,
+                                 size_t workspace_bytes, spq_stream_t stream) {
+  SPQ_REQUIRE(dx || dweight || dbias, "spq_layernorm_bwd: null pointer (no output requested)");
+  SPQ_REQUIRE(g && (!(dx || dweight) || (x && mean && den)) && (!dx || weight), "spq_layernorm_bwd: null pointer");
+  SPQ_REQUIRE(rows > 0 && cols > 0, "spq_layernorm_bwd: empty tensor");
+  if (!ln_cols_ok(cols) || !aligned16(g) || !aligned16(x) || !aligned16(weight) || !aligned16(dx)) {
+    set_error("spq_layernorm_bwd: needs cols %% 4 == 0, cols <= 8192 and 16-byte aligned tensors (cols = %lld)", (long long)cols);
+    return SPQ_ERR_UNSUPPORTED;
+  }
+  const bool sums = dweight || dbias;
+  if (sums && (!workspace || !aligned16(workspace) || workspace_bytes < spq_layernorm_bwd_workspace_bytes(rows, cols))) {
+    set_error("spq_layernorm_bwd: workspace too small or misaligned (%zu bytes, needs %zu)", workspace_bytes,
+              spq_layernorm_bwd_workspace_bytes(rows, cols));
+    return SPQ_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t S = ln_bwd_slabs(rows);
+  const int nv = (int)ceil_div64(cols, 256), c = (int)cols;
+  const int acc = dweight ? 2 : (dbias ? 1 : 0);
+  float* part = (float*)workspace;
+  if (nv <= 8 || dx) {
+    const unsigned grid = (unsigned)S;
+    if (nv <= 2) ln_bwd_rows_launch<2>(dx != nullptr, acc, grid, st, g, x, mean, den, weight, rows, c, S, dx, part);
+    else if (nv <= 4) ln_bwd_rows_launch<4>(dx != nullptr, acc, grid, st, g, x, mean, den, weight, rows, c, S, dx, part);
+    else if (nv <= 8) ln_bwd_rows_launch<8>(dx != nullptr, acc, grid, st, g, x, mean, den, weight, rows, c, S, dx, part);
+    else if (nv <= 16) ln_bwd_rows_launch<16>(true, 0, grid, st, g, x, mean, den, weight, rows, c, S, dx, part);
+    else ln_bwd_rows_launch<32>(true, 0, grid, st, g, x, mean, den, weight, rows, c, S, dx, part);
+    int rc = check_launch("spq_layernorm_bwd(rows)");
+    if (rc) return rc;
+  }
+  if (!sums) return SPQ_OK;
+  if (nv > 8) {
+    const dim3 grid((unsigned)ceil_div64(cols, 256), (unsigned)S);
+    if (dweight) ln_bwd_cols_kernel<true><<<grid, 256, 0, st>>>(g, x, mean, den, rows, c, S, part);
+    else ln_bwd_cols_kernel<false><<<grid, 256, 0, st>>>(g, x, mean, den, rows, c, S, part);
+    int rc = check_launch("spq_layernorm_bwd(columns)");
+    if (rc) return rc;
+  }
+  ln_bwd_merge_kernel<<<(unsigned)ceil_div64(cols, 64), 1024, 0, st>>>(part, S, c, dweight, dbias);
+  return check_launch("spq_layernorm_bwd(merge)");
 }
 
 extern "C" int spq_dynamic_limb_scale(const float* x, int64_t n, float* scale_out2, void* workspace,
