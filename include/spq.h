@@ -186,6 +186,24 @@ int spq_layernorm_bwd(const float* g, const float* x, const float* mean, const f
                       spq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The causal attention core between c_attn and c_proj (models_sp.py:61-75: split heads, q k^T / sqrt(d), lower-triangular
+ * mask, softmax, times v, merge heads), forward, as ONE flash-style launch on the fp32-input MFMA:
+ *     out[b, t, h d + :] = sum_{j <= t} softmax_j(q[b,t,h] . k[b,j,h] / sqrt(d)) v[b,j,h]
+ * qkv: c_attn's output as it lies in memory, [B T, 3 C] row-major, C = n_head * head_dim; head h has q at columns h d,
+ *      k at C + h d, v at 2 C + h d.  out: [B T, C], heads merged.  No transposed or contiguous intermediate, no T x T matrix.
+ * lse (nullable): [B, n_head, T], the natural-log sum-exp of the row's scaled, masked scores (what a backward needs); `out`
+ *      is bit-identical with and without it.
+ * Domain: head_dim 64 (every GPT-2 size), also 16, 32, 80 and 128; any B, T, n_head >= 1; 16-byte aligned pointers.  Anything else
+ * returns SPQ_ERR_UNSUPPORTED before anything is enqueued.  No workspace, no allocation, no host synchronisation; capturable.
+ * Deterministic (no atomics).  Row (b, t) is a function of rows <= t of sequence b alone: its bits do not change with B, with the
+ * place of the sequence in the batch, or with T (the first T' rows of a longer call are the call with T = T').  NaN: a NaN in
+ * q-row t makes row t NaN, one in k-row j rows >= j of that head; a non-finite v-row j rows >= j and the rows before it in its
+ * own 32-key tile (32 floor(j/32) .. j-1), where the masked product is 0 * NaN -- the dense formula spreads it to every row.
+ * ------------------------------------------------------------------------------------------------- */
+int spq_causal_attention_fwd(const float* qkv, int64_t B, int64_t T, int64_t n_head, int64_t head_dim, float* out,
+                             float* lse /* may be NULL */, spq_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * The path's only exchange step: before finish_calibration every rank merges the running
  * statistics of its input quantizers (quantization.py:202-207 across ranks) with ONE in-place
  * all-reduce(MAX) over the flat fp32 buffer [-min_0 .. | max_0 ..] -- ncclAllReduce(ncclFloat, ncclMax) of

@@ -10,11 +10,13 @@ from .fake_quantize import (LearnableFakeQuantize, LogQuantizationFunction, MinM
 from .sp_linear import LoRALayer, SPLinearWithLoRA
 from .calibration import SpqComm, allreduce_calibration_stats, calibrate_layer, calibrate_model
 from . import cpt, deploy, synthetic
-from .blocks import SPMLP, SPAttention, SPBlock, SPLMHeadModel, SPModel, SwitchableLayerNorm
+from .blocks import SPMLP, SPAttention, SPBlock, SPLMHeadModel, SPModel, SwitchableLayerNorm, set_attention_core
+from .attention import causal_attention
 from .cpt import CPTLinear, LoRAAdapter, GradientQuantizer, calibrate_cpt_layer, calibrate_cpt_model, cpt_mlp_forward
 from .graphs import GraphedForward
 
 __all__ = ["SPLinearWithLoRA", "LoRALayer", "LearnableFakeQuantize", "MinMaxQuantizationFunction",
            "LogQuantizationFunction", "apply_minmax_quantization", "apply_log_quantization", "fake_quantize",
            "allreduce_calibration_stats", "calibrate_layer", "calibrate_model", "SpqComm",
-           "SwitchableLayerNorm", "SPMLP", "SPAttention", "SPBlock", "SPModel", "SPLMHeadModel", "deploy", "cpt", "CPTLinear", "LoRAAdapter", "GradientQuantizer", "calibrate_cpt_layer", "calibrate_cpt_model", "cpt_mlp_forward", "GraphedForward"]
+           "SwitchableLayerNorm", "SPMLP", "SPAttention", "SPBlock", "SPModel", "SPLMHeadModel", "deploy", "cpt", "CPTLinear", "LoRAAdapter", "GradientQuantizer", "calibrate_cpt_layer", "calibrate_cpt_model", "cpt_mlp_forward", "GraphedForward",
+           "causal_attention", "set_attention_core"]

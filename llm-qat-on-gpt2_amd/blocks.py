@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from . import _lib, attention
 from .sp_linear import SPLinearWithLoRA
 
 
@@ -194,8 +194,9 @@ class SPMLP(nn.Module):
 
 
 class SPAttention(nn.Module):
-    """models_sp.py:18-74: fused QKV projection, causal softmax attention (stock torch-ROCm ops, not on the quantized
-    path), output projection -- on the drop-in linears."""
+    """models_sp.py:18-74: fused QKV projection, causal softmax attention, output projection -- on the drop-in linears.  The
+    attention core is not on the quantized path; it runs on torch-ROCm's fused kernel by default (``use_sdpa``), on the
+    library's own HIP kernel with ``use_hip_core`` (forward without a gradient only), or as the reference's explicit formula."""
 
     def __init__(self, config, bit_widths):
         super().__init__()
@@ -210,6 +211,7 @@ class SPAttention(nn.Module):
         self.c_proj = SPLinearWithLoRA(config.n_embd, config.n_embd, **common)
         self.register_buffer("bias", torch.tril(torch.ones(config.n_positions, config.n_positions)))
         self.use_sdpa = True        # False: the reference's explicit q k^T / softmax / v formula (models_sp.py:66-71)
+        self.use_hip_core = False   # True: spq_causal_attention_fwd where it applies (see core), else the path above
 
     def set_precision(self, bits) -> int:
         self.current_bit_width = bits
@@ -224,6 +226,12 @@ class SPAttention(nn.Module):
         """models_sp.py:61-75: what sits between the two projections (split heads, causal softmax attention, merge heads)."""
         B, T, _ = qkv.shape
         C = self.n_embd
+        if (self.use_hip_core and not (torch.is_grad_enabled() and qkv.requires_grad) and qkv.shape[2] == 3 * C
+                and attention.served(qkv, self.n_head)):
+            # one launch from c_attn's output to c_proj's input: no head split / merge copies (the core holds no quantizer, so
+            # a statistics pass needs nothing else from it).  Anything it does not serve -- a gradient, a CPU or non-fp32 or
+            # strided tensor, another head size -- takes the path below, unchanged.
+            return attention.causal_attention(qkv, self.n_head)
         q, k, v = qkv.split(self.n_embd, dim=2)
         q = q.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         k = k.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
@@ -237,6 +245,23 @@ class SPAttention(nn.Module):
             att = att.masked_fill(self.bias[:T, :T].to(att.device) == 0, float('-inf'))
             out = torch.softmax(att, dim=-1) @ v
         return out.transpose(1, 2).contiguous().view(B, T, C)
+
+
+ATTENTION_CORES = ('hip', 'sdpa', 'explicit')
+
+
+def set_attention_core(model: nn.Module, core: str) -> int:
+    """Choose the attention core of every ``SPAttention`` in ``model``: 'hip' (spq_causal_attention_fwd where it applies, SDPA
+    elsewhere), 'sdpa' (the default) or 'explicit' (the reference's formula).  Returns the number of modules set."""
+    if core not in ATTENTION_CORES:
+        raise ValueError(f"attention core must be one of {ATTENTION_CORES}, got {core!r}")
+    n = 0
+    for m in model.modules():
+        if isinstance(m, SPAttention):
+            m.use_hip_core = core == 'hip'
+            m.use_sdpa = core != 'explicit'
+            n += 1
+    return n
 
 
 class SPBlock(nn.Module):
