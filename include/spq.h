@@ -204,6 +204,26 @@ int spq_causal_attention_fwd(const float* qkv, int64_t B, int64_t T, int64_t n_h
                              float* lse /* may be NULL */, spq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The backward of that core, recomputing the probabilities from `lse`.  With s = q k^T / sqrt(d) masked causally,
+ *     P = exp(s - lse),  delta_i = sum_d dout_i out_i,  dv_j = sum_{i>=j} P_ij dout_i,  dS_ij = P_ij (dout_i . v_j - delta_i),
+ *     dq_i = sum_{j<=i} dS_ij k_j / sqrt(d),  dk_j = sum_{i>=j} dS_ij q_i / sqrt(d)
+ * qkv, out, lse: the forward's input and outputs.  dout: [B T, C], the gradient of `out`, heads merged.  dqkv: [B T, 3 C], the
+ * gradient of qkv in qkv's own layout (dq | dk | dv, head h at columns h d of each third); every element is written.
+ * workspace: spq_causal_attention_bwd_workspace_bytes(B, T, n_head, head_dim) bytes (delta, [B, n_head, T]), 16-byte aligned.
+ * Domain: head_dim 64, also 16 and 32; any B, T, n_head >= 1; 16-byte aligned pointers.  An unserved head_dim, a size below 1,
+ * a problem too large for one launch, a misaligned pointer or a short workspace returns SPQ_ERR_UNSUPPORTED, a null pointer
+ * SPQ_ERR_INVALID, both before anything is enqueued; spq_causal_attention_bwd_workspace_bytes returns SPQ_ERR_UNSUPPORTED
+ * (negative) for a shape the call would refuse.  No allocation, no host synchronisation; capturable.  Three launches.
+ * Deterministic: no atomics, and every element is summed in one fixed order that depends on its query / key index alone (32-wide
+ * tiles anchored at position 0 along both axes), so the gradient of a sequence does not change with B or with its place in the
+ * batch, and with dout rows >= T' all zero the first T' rows are the call with T = T'.  (sequence, head) pairs never meet.
+ * ------------------------------------------------------------------------------------------------- */
+int64_t spq_causal_attention_bwd_workspace_bytes(int64_t B, int64_t T, int64_t n_head, int64_t head_dim);
+int spq_causal_attention_bwd(const float* qkv, const float* out, const float* lse, const float* dout, int64_t B, int64_t T,
+                             int64_t n_head, int64_t head_dim, float* dqkv, void* workspace, size_t workspace_bytes,
+                             spq_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * The path's only exchange step: before finish_calibration every rank merges the running
  * statistics of its input quantizers (quantization.py:202-207 across ranks) with ONE in-place
  * all-reduce(MAX) over the flat fp32 buffer [-min_0 .. | max_0 ..] -- ncclAllReduce(ncclFloat, ncclMax) of

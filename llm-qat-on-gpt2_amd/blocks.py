@@ -196,7 +196,8 @@ class SPMLP(nn.Module):
 class SPAttention(nn.Module):
     """models_sp.py:18-74: fused QKV projection, causal softmax attention, output projection -- on the drop-in linears.  The
     attention core is not on the quantized path; it runs on torch-ROCm's fused kernel by default (``use_sdpa``), on the
-    library's own HIP kernel with ``use_hip_core`` (forward without a gradient only), or as the reference's explicit formula."""
+    library's own HIP kernel with ``use_hip_core`` (without a gradient; with ``use_hip_backward`` also under one, on the HIP
+    backward), or as the reference's explicit formula."""
 
     def __init__(self, config, bit_widths):
         super().__init__()
@@ -212,6 +213,7 @@ class SPAttention(nn.Module):
         self.register_buffer("bias", torch.tril(torch.ones(config.n_positions, config.n_positions)))
         self.use_sdpa = True        # False: the reference's explicit q k^T / softmax / v formula (models_sp.py:66-71)
         self.use_hip_core = False   # True: spq_causal_attention_fwd where it applies (see core), else the path above
+        self.use_hip_backward = False   # True (with use_hip_core): a call that needs a gradient takes the HIP forward / backward pair
 
     def set_precision(self, bits) -> int:
         self.current_bit_width = bits
@@ -232,6 +234,10 @@ class SPAttention(nn.Module):
             # a statistics pass needs nothing else from it).  Anything it does not serve -- a gradient, a CPU or non-fp32 or
             # strided tensor, another head size -- takes the path below, unchanged.
             return attention.causal_attention(qkv, self.n_head)
+        if (self.use_hip_core and self.use_hip_backward and torch.is_grad_enabled() and qkv.requires_grad and qkv.shape[2] == 3 * C
+                and attention.served_backward(qkv, self.n_head)):
+            # the same launch under autograd, spq_causal_attention_bwd on the way back (qkv, out and lse are what it keeps)
+            return attention.causal_attention_autograd(qkv, self.n_head)
         q, k, v = qkv.split(self.n_embd, dim=2)
         q = q.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
         k = k.view(B, T, self.n_head, self.head_dim).transpose(1, 2)
@@ -250,15 +256,17 @@ class SPAttention(nn.Module):
 ATTENTION_CORES = ('hip', 'sdpa', 'explicit')
 
 
-def set_attention_core(model: nn.Module, core: str) -> int:
+def set_attention_core(model: nn.Module, core: str, backward: bool = False) -> int:
     """Choose the attention core of every ``SPAttention`` in ``model``: 'hip' (spq_causal_attention_fwd where it applies, SDPA
-    elsewhere), 'sdpa' (the default) or 'explicit' (the reference's formula).  Returns the number of modules set."""
+    elsewhere), 'sdpa' (the default) or 'explicit' (the reference's formula).  ``backward`` (with 'hip' only): calls that need a
+    gradient take the HIP forward / backward pair where it applies; off, they stay on SDPA.  Returns the number of modules set."""
     if core not in ATTENTION_CORES:
         raise ValueError(f"attention core must be one of {ATTENTION_CORES}, got {core!r}")
     n = 0
     for m in model.modules():
         if isinstance(m, SPAttention):
             m.use_hip_core = core == 'hip'
+            m.use_hip_backward = core == 'hip' and bool(backward)
             m.use_sdpa = core != 'explicit'
             n += 1
     return n
