@@ -5,17 +5,18 @@
 //   dS_ij = P_ij (dP_ij - delta_i)     dQ_i = sum_{j<=i} dS_ij K_j / sqrt(D)     dK_j = sum_{i>=j} dS_ij Q_i / sqrt(D)
 //
 // qkv [B*T, 3C] is read where it lies, dout / out [B*T, C] with the heads merged, and dqkv [B*T, 3C] = dq | dk | dv is written in
-// c_attn's own layout: no transposed copy, no cat, no T x T matrix in memory.  Three launches:
+// c_attn's own layout: no transposed copy, no cat, no T x T matrix in memory.  Three launches on the forward's tile plan (operand
+// maps and the "rows" / "cols" LDS images: spq_attention_tile.h):
 //
 //   delta    the diagonal of O . dO^T, 32 rows per wavefront on the MFMA in the summation order of dP -> workspace [B, H, T].
 //   dQ       mirrors the forward.  One 256-thread workgroup = 128 queries, wavefront w owns 32 of them (lane & 31 = query) and
 //            walks the 32-key tiles, anchored at position 0, up to its diagonal.  Q^T and dO^T stay in registers as the B operands
-//            of S^T = K . Q^T and dP^T = V . dO^T (A = the K / V tile from LDS [key][D + 4]); dS^T is born in the C/D registers
-//            and is, as it is, the B operand of dQ^T += K^T . dS^T (A = K^T from an LDS image [d][32 keys + 4]).
+//            of S^T = K . Q^T and dP^T = V . dO^T (A = the K / V tile as a "rows" image); dS^T is born in the C/D registers
+//            and is, as it is, the B operand of dQ^T += K^T . dS^T (A = the K tile as a "cols" image).
 //   dK/dV    the same plan with the roles swapped.  A workgroup owns 128 keys, wavefront w 32 of them (lane & 31 = key) with
 //            K^T and V^T in registers, and walks the 32-query tiles, anchored at position 0, from its diagonal to the end:
-//            S = Q . K^T and dP = dO . V^T (A = the Q / dO tile from LDS [query][D + 4]), then dV^T += dO^T . P and
-//            dK^T += Q^T . dS with A from the transposed LDS images and B = the registers P / dS were born in.  lse and delta of
+//            S = Q . K^T and dP = dO . V^T (A = the Q / dO tile as a "rows" image), then dV^T += dO^T . P and
+//            dK^T += Q^T . dS with A from the "cols" images and B = the registers P / dS were born in.  lse and delta of
 //            the tile's 32 queries go through LDS.  The first workgroup indices get the first key tiles: the longest walks.
 //
 // Only the diagonal tile is masked: there P and dS are forced to exactly 0 (not left to exp of -inf times something).  Rows at
@@ -26,13 +27,9 @@
 // of the sequence in the batch or on the grid, and runs repeat bit for bit.  (b, h) pairs never meet: a NaN stays in its head.
 #include <math.h>
 
-#include "spq_common.h"
+#include "spq_attention_tile.h"
 
 namespace spq {
-
-typedef float attb_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int ATTB_BLOCK = 128, ATTB_TILE = 32, ATTB_TLD = ATTB_TILE + 4;
 
 struct AttBwdArgs {
   const float* qkv; const float* out; const float* lse; const float* dout; const float* delta;
@@ -41,124 +38,6 @@ struct AttBwdArgs {
   float sqrt_d;
 };
 
-// ---- one 32-row tile on its way global -> registers -> LDS, in either of two images -------------------------------------
-// "rows": float4 along d -> LDS [row][D + 4];  "cols": 4 consecutive rows of one d -> LDS [d][32 rows + 4]
-template <int D>
-struct AttbRows { static constexpr int N = (ATTB_TILE * D / 4 + 255) / 256; float4 r[N]; };
-template <int D>
-struct AttbCols { static constexpr int N = (D * (ATTB_TILE / 4) + 255) / 256; float4 r[N]; };
-
-template <int D>
-__device__ __forceinline__ void attb_load_rows(AttbRows<D>& t, const float* __restrict__ base, int64_t ld, int r0, int T, int tid) {
-#pragma unroll
-  for (int i = 0; i < AttbRows<D>::N; ++i) {
-    const int idx = tid + 256 * i;
-    const int row = idx / (D / 4), c = (idx % (D / 4)) * 4;
-    float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (idx < ATTB_TILE * D / 4 && r0 + row < T) val = *reinterpret_cast<const float4*>(base + (int64_t)(r0 + row) * ld + c);
-    t.r[i] = val;
-  }
-}
-
-template <int D>
-__device__ __forceinline__ void attb_store_rows(const AttbRows<D>& t, float* __restrict__ s, int tid) {
-#pragma unroll
-  for (int i = 0; i < AttbRows<D>::N; ++i) {
-    const int idx = tid + 256 * i;
-    if (idx < ATTB_TILE * D / 4) *reinterpret_cast<float4*>(s + (idx / (D / 4)) * (D + 4) + (idx % (D / 4)) * 4) = t.r[i];
-  }
-}
-
-template <int D>
-__device__ __forceinline__ void attb_load_cols(AttbCols<D>& t, const float* __restrict__ base, int64_t ld, int r0, int T, int tid) {
-#pragma unroll
-  for (int i = 0; i < AttbCols<D>::N; ++i) {
-    const int idx = tid + 256 * i;
-    const int d = idx % D, row = r0 + (idx / D) * 4;
-    float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (idx < D * (ATTB_TILE / 4)) {
-      const float* p = base + (int64_t)row * ld + d;
-      if (row + 0 < T) val.x = p[0];
-      if (row + 1 < T) val.y = p[ld];
-      if (row + 2 < T) val.z = p[2 * ld];
-      if (row + 3 < T) val.w = p[3 * ld];
-    }
-    t.r[i] = val;
-  }
-}
-
-template <int D>
-__device__ __forceinline__ void attb_store_cols(const AttbCols<D>& t, float* __restrict__ s, int tid) {
-#pragma unroll
-  for (int i = 0; i < AttbCols<D>::N; ++i) {
-    const int idx = tid + 256 * i;
-    if (idx < D * (ATTB_TILE / 4)) *reinterpret_cast<float4*>(s + (idx % D) * ATTB_TLD + (idx / D) * 4) = t.r[i];
-  }
-}
-
-// C = A . B with A = a 32-row tile from LDS [row][D + 4] (lane half h reads the D/2 contiguous d of its row), B = D/2 registers
-// holding the same d of this lane's column (the forward's S^T = K . Q^T)
-template <int D>
-__device__ __forceinline__ attb_f32x16 attb_rows_times_regs(const float* __restrict__ ap, const float (&b)[D / 2]) {
-  attb_f32x16 c;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) c[e] = 0.f;
-#pragma unroll
-  for (int i = 0; i < D / 8; ++i) {
-    const float4 a = *reinterpret_cast<const float4*>(ap + 4 * i);
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b[4 * i + 0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b[4 * i + 1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b[4 * i + 2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b[4 * i + 3], c, 0, 0, 0);
-  }
-  return c;
-}
-
-// acc[d block] += A . B with A = the transposed LDS image [d][32 + 4] and B = a C/D register set as it was born (step r sums the
-// rows 4h + (r & 3) + 8 (r >> 2), h = 0, 1 -- the forward's O^T += V^T . P^T)
-template <int NDB>
-__device__ __forceinline__ void attb_cols_times_cd(attb_f32x16 (&acc)[NDB], const float* __restrict__ ap, const attb_f32x16& b) {
-#pragma unroll
-  for (int gi = 0; gi < 4; ++gi) {
-#pragma unroll
-    for (int i = 0; i < NDB; ++i) {
-      const float4 a = *reinterpret_cast<const float4*>(ap + i * 32 * ATTB_TLD + 8 * gi);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b[4 * gi + 0], acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b[4 * gi + 1], acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b[4 * gi + 2], acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b[4 * gi + 3], acc[i], 0, 0, 0);
-    }
-  }
-}
-
-// D/2 floats of one row into registers, times `scale`
-template <int D>
-__device__ __forceinline__ void attb_load_half_row(float (&r)[D / 2], const float* __restrict__ p, float scale) {
-#pragma unroll
-  for (int i = 0; i < D / 8; ++i) {
-    const float4 v4 = *reinterpret_cast<const float4*>(p + 4 * i);
-    r[4 * i + 0] = v4.x * scale; r[4 * i + 1] = v4.y * scale; r[4 * i + 2] = v4.z * scale; r[4 * i + 3] = v4.w * scale;
-  }
-}
-
-// the C/D register set of one accumulator block (rows = d) -> D floats of this lane's row, each times `mul` or over `div`
-template <int D, int NDB, bool POW2>
-__device__ __forceinline__ void attb_store_acc(const attb_f32x16 (&acc)[NDB], float* __restrict__ op, int h, float mul, float div) {
-#pragma unroll
-  for (int i = 0; i < NDB; ++i) {
-#pragma unroll
-    for (int gi = 0; gi < 4; ++gi) {
-      const int dd = i * 32 + 8 * gi + 4 * h;
-      if (dd < D) {
-        float4 v4;
-        if (POW2) v4 = make_float4(acc[i][4 * gi + 0] * mul, acc[i][4 * gi + 1] * mul, acc[i][4 * gi + 2] * mul, acc[i][4 * gi + 3] * mul);
-        else v4 = make_float4(acc[i][4 * gi + 0] / div, acc[i][4 * gi + 1] / div, acc[i][4 * gi + 2] / div, acc[i][4 * gi + 3] / div);
-        *reinterpret_cast<float4*>(op + dd) = v4;
-      }
-    }
-  }
-}
-
 // ---- delta[b, h, t] = sum_d dO[b, t, h D + d] O[b, t, h D + d] --------------------------------------------------------------
 // The diagonal of O . dO^T on the MFMA, with O where the walks have V: delta is then summed in exactly the order of dP = dO . V^T,
 // so where O is V bit for bit (a row that attends to one key) dP - delta is exactly 0.  Wavefront w = 32 rows, no LDS.
@@ -166,20 +45,16 @@ template <int D>
 __global__ __launch_bounds__(256) void causal_attention_bwd_delta_kernel(AttBwdArgs g) {
   constexpr int HALF = D / 2;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31, h = lane >> 5;
-  const int qt = (int)(blockIdx.x / (unsigned)g.BH), bh = (int)(blockIdx.x % (unsigned)g.BH);
-  const int b = bh / g.H, hd = bh % g.H;
   const int T = g.T;
-  const int64_t C = (int64_t)g.H * D;
-  const int qw0 = qt * ATTB_BLOCK + 32 * w;
-  if (qw0 >= T) return;                          // wavefront-uniform; the kernel has no barrier
-  const int qrow = qw0 + l31;
-  const int64_t off = ((int64_t)b * T + min(qrow, T - 1)) * C + (int64_t)hd * D + HALF * h;
+  const AttWork wk = att_work(g.n_blk, false, g.BH, g.H, D, T, w);
+  if (!wk.active) return;                        // wavefront-uniform; the kernel has no barrier
+  const int qrow = wk.row0 + l31;
+  const int64_t off = ((int64_t)wk.b * T + min(qrow, T - 1)) * wk.C + (int64_t)wk.hd * D + HALF * h;
   float o[HALF], dO[HALF];
-  attb_load_half_row<D>(o, g.out + off, 1.0f);
-  attb_load_half_row<D>(dO, g.dout + off, 1.0f);
-  attb_f32x16 c;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) c[e] = 0.f;
+  att_load_half_row<D>(o, g.out + off, 1.0f);
+  att_load_half_row<D>(dO, g.dout + off, 1.0f);
+  att_f32x16 c;
+  att_zero(c);
 #pragma unroll
   for (int i = 0; i < HALF; ++i) c = __builtin_amdgcn_mfma_f32_32x32x2f32(o[i], dO[i], c, 0, 0, 0);
   // row l31 of column l31 lies in register (l31 & 3) + 4 (l31 >> 3) of lane half (l31 >> 2) & 1
@@ -190,68 +65,59 @@ __global__ __launch_bounds__(256) void causal_attention_bwd_delta_kernel(AttBwdA
     if (e == e_mine) mine = c[e];
   const float other = __shfl_xor(mine, 32, 64);
   const float delta = (((l31 >> 2) & 1) == h) ? mine : other;
-  if (h == 0 && qrow < T) g.delta_out[(int64_t)bh * T + qrow] = delta;
+  if (h == 0 && qrow < T) g.delta_out[(int64_t)wk.bh * T + qrow] = delta;
 }
 
 // ---- dQ ---------------------------------------------------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256, 2) void causal_attention_bwd_dq_kernel(AttBwdArgs g) {
   constexpr int HALF = D / 2, KLD = D + 4, NDB = (D + 31) / 32;
-  constexpr bool POW2 = (D == 16 || D == 64);    // as the forward: 1 / sqrt(D) a power of two -> q is scaled, else the score divided
-  __shared__ __attribute__((aligned(16))) float Ks[ATTB_TILE * KLD];
-  __shared__ __attribute__((aligned(16))) float Vs[ATTB_TILE * KLD];
-  __shared__ __attribute__((aligned(16))) float Kt[NDB * 32 * ATTB_TLD];   // rows >= D (D = 16) are never written: they feed only the
-                                                                           // accumulator rows >= D, which are never stored
+  constexpr bool POW2 = att_scale_is_pow2(D);    // as the forward: q is scaled, else the score divided
+  __shared__ __attribute__((aligned(16))) float Ks[ATT_TILE * KLD];
+  __shared__ __attribute__((aligned(16))) float Vs[ATT_TILE * KLD];
+  __shared__ __attribute__((aligned(16))) float Kt[NDB * 32 * ATT_TLD];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31, h = lane >> 5;
-  const int qt = g.n_blk - 1 - (int)(blockIdx.x / (unsigned)g.BH);         // long query tiles first
-  const int bh = (int)(blockIdx.x % (unsigned)g.BH);
-  const int b = bh / g.H, hd = bh % g.H;
   const int T = g.T;
-  const int64_t C = (int64_t)g.H * D, ld = 3 * C;
-  const float* base = g.qkv + (int64_t)b * T * ld + (int64_t)hd * D;
+  const AttWork wk = att_work(g.n_blk, true, g.BH, g.H, D, T, w);          // long query tiles first
+  const int qt = wk.blk;
+  const int64_t C = wk.C, ld = wk.ld;
+  const float* base = g.qkv + (int64_t)wk.b * T * ld + (int64_t)wk.hd * D;
   const float* kbase = base + C;
   const float* vbase = base + 2 * C;
-
-  const int qw0 = qt * ATTB_BLOCK + 32 * w;
-  const int qrow = qw0 + l31, qclamp = min(qrow, T - 1);
-  const bool active = qw0 < T;                   // wavefront-uniform
-  const int my_diag = qw0 / ATTB_TILE;
-  const int kt_last = min(qt * (ATTB_BLOCK / ATTB_TILE) + (ATTB_BLOCK / ATTB_TILE - 1), (T - 1) / ATTB_TILE);
+  const int qrow = wk.row0 + l31, qclamp = min(qrow, T - 1);
+  const int kt_last = min(qt * (ATT_BLOCK / ATT_TILE) + (ATT_BLOCK / ATT_TILE - 1), (T - 1) / ATT_TILE);
 
   float q[HALF], dO[HALF];
-  attb_load_half_row<D>(q, base + (int64_t)qclamp * ld + HALF * h, POW2 ? 1.0f / g.sqrt_d : 1.0f);
-  attb_load_half_row<D>(dO, g.dout + ((int64_t)b * T + qclamp) * C + (int64_t)hd * D + HALF * h, 1.0f);
-  const float lse_q = g.lse[(int64_t)bh * T + qclamp];
-  const float delta_q = g.delta[(int64_t)bh * T + qclamp];
+  att_load_half_row<D>(q, base + (int64_t)qclamp * ld + HALF * h, POW2 ? 1.0f / g.sqrt_d : 1.0f);
+  att_load_half_row<D>(dO, g.dout + ((int64_t)wk.b * T + qclamp) * C + (int64_t)wk.hd * D + HALF * h, 1.0f);
+  const float lse_q = g.lse[(int64_t)wk.bh * T + qclamp];
+  const float delta_q = g.delta[(int64_t)wk.bh * T + qclamp];
 
-  attb_f32x16 acc[NDB];
-#pragma unroll
-  for (int i = 0; i < NDB; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
+  att_f32x16 acc[NDB];
+  att_zero(acc);
 
-  AttbRows<D> rk, rv;
-  AttbCols<D> ck;
-  attb_load_rows<D>(rk, kbase, ld, 0, T, tid);
-  attb_load_rows<D>(rv, vbase, ld, 0, T, tid);
-  attb_load_cols<D>(ck, kbase, ld, 0, T, tid);
+  AttRows<D> rk, rv;
+  AttCols<D> ck;
+  att_load_rows<D>(rk, kbase, ld, 0, T, tid);
+  att_load_rows<D>(rv, vbase, ld, 0, T, tid);
+  att_load_cols<D>(ck, kbase, ld, 0, T, tid);
   for (int kt = 0; kt <= kt_last; ++kt) {
     __syncthreads();                             // the previous tile's fragment reads are done
-    attb_store_rows<D>(rk, Ks, tid);
-    attb_store_rows<D>(rv, Vs, tid);
-    attb_store_cols<D>(ck, Kt, tid);
+    att_store_rows<D>(rk, Ks, tid);
+    att_store_rows<D>(rv, Vs, tid);
+    att_store_cols<D>(ck, Kt, tid);
     __syncthreads();
     if (kt < kt_last) {
-      attb_load_rows<D>(rk, kbase, ld, (kt + 1) * ATTB_TILE, T, tid);
-      attb_load_rows<D>(rv, vbase, ld, (kt + 1) * ATTB_TILE, T, tid);
-      attb_load_cols<D>(ck, kbase, ld, (kt + 1) * ATTB_TILE, T, tid);
+      att_load_rows<D>(rk, kbase, ld, (kt + 1) * ATT_TILE, T, tid);
+      att_load_rows<D>(rv, vbase, ld, (kt + 1) * ATT_TILE, T, tid);
+      att_load_cols<D>(ck, kbase, ld, (kt + 1) * ATT_TILE, T, tid);
     }
-    if (!active || kt > my_diag) continue;       // above this wavefront's diagonal (it still moves tiles for the others)
+    if (!wk.active || kt > wk.diag) continue;    // above this wavefront's diagonal (it still moves tiles for the others)
 
     // ---- S^T = K . Q^T and dP^T = V . dO^T: register e of lane half h = key 4h + (e & 3) + 8 (e >> 2), lane & 31 = query
-    attb_f32x16 s = attb_rows_times_regs<D>(Ks + l31 * KLD + HALF * h, q);
-    const attb_f32x16 dp = attb_rows_times_regs<D>(Vs + l31 * KLD + HALF * h, dO);
-    const bool diag = kt == my_diag;
+    att_f32x16 s = att_rows_times_regs<D>(Ks + l31 * KLD + HALF * h, q);
+    const att_f32x16 dp = att_rows_times_regs<D>(Vs + l31 * KLD + HALF * h, dO);
+    const bool diag = kt == wk.diag;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const bool masked = diag && (4 * h + (e & 3) + 8 * (e >> 2) > l31);
@@ -260,83 +126,76 @@ __global__ __launch_bounds__(256, 2) void causal_attention_bwd_dq_kernel(AttBwdA
       s[e] = masked ? 0.f : p * (dp[e] - delta_q);                     // dS^T (exactly 0 where masked, whatever dP is)
     }
     // ---- dQ^T += K^T . dS^T
-    attb_cols_times_cd<NDB>(acc, Kt + l31 * ATTB_TLD + 4 * h, s);
+    att_cols_times_cd<NDB>(acc, Kt + l31 * ATT_TLD + 4 * h, s);
   }
 
-  if (!active || qrow >= T) return;
-  attb_store_acc<D, NDB, POW2>(acc, g.dqkv + ((int64_t)b * T + qrow) * ld + (int64_t)hd * D, h, 1.0f / g.sqrt_d, g.sqrt_d);
+  if (!wk.active || qrow >= T) return;
+  att_store_acc<D, NDB, POW2>(acc, g.dqkv + ((int64_t)wk.b * T + qrow) * ld + (int64_t)wk.hd * D, h, 1.0f / g.sqrt_d, g.sqrt_d);
 }
 
 // ---- dK and dV --------------------------------------------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256, 1) void causal_attention_bwd_dkv_kernel(AttBwdArgs g) {
   constexpr int HALF = D / 2, KLD = D + 4, NDB = (D + 31) / 32;
-  constexpr bool POW2 = (D == 16 || D == 64);
-  __shared__ __attribute__((aligned(16))) float Qs[ATTB_TILE * KLD];
-  __shared__ __attribute__((aligned(16))) float Gs[ATTB_TILE * KLD];       // the dO tile
-  __shared__ __attribute__((aligned(16))) float Qt[NDB * 32 * ATTB_TLD];
-  __shared__ __attribute__((aligned(16))) float Gt[NDB * 32 * ATTB_TLD];
-  __shared__ __attribute__((aligned(16))) float Ls[ATTB_TILE];             // lse and delta of the tile's queries
-  __shared__ __attribute__((aligned(16))) float Ds[ATTB_TILE];
+  constexpr bool POW2 = att_scale_is_pow2(D);
+  __shared__ __attribute__((aligned(16))) float Qs[ATT_TILE * KLD];
+  __shared__ __attribute__((aligned(16))) float Gs[ATT_TILE * KLD];       // the dO tile
+  __shared__ __attribute__((aligned(16))) float Qt[NDB * 32 * ATT_TLD];
+  __shared__ __attribute__((aligned(16))) float Gt[NDB * 32 * ATT_TLD];
+  __shared__ __attribute__((aligned(16))) float Ls[ATT_TILE];             // lse and delta of the tile's queries
+  __shared__ __attribute__((aligned(16))) float Ds[ATT_TILE];
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31, h = lane >> 5;
-  const int kb = (int)(blockIdx.x / (unsigned)g.BH);                       // first key blocks first: the longest walks
-  const int bh = (int)(blockIdx.x % (unsigned)g.BH);
-  const int b = bh / g.H, hd = bh % g.H;
   const int T = g.T;
-  const int64_t C = (int64_t)g.H * D, ld = 3 * C;
-  const float* qbase = g.qkv + (int64_t)b * T * ld + (int64_t)hd * D;
-  const float* gbase = g.dout + (int64_t)b * T * C + (int64_t)hd * D;
-  const float* lbase = g.lse + (int64_t)bh * T;
-  const float* dbase = g.delta + (int64_t)bh * T;
-
-  const int kw0 = kb * ATTB_BLOCK + 32 * w;      // first key of this wavefront; its diagonal query tile starts there too
-  const int krow = kw0 + l31, kclamp = min(krow, T - 1);
-  const bool active = kw0 < T;                   // wavefront-uniform
-  const int my_diag = kw0 / ATTB_TILE;
-  const int qt_first = kb * (ATTB_BLOCK / ATTB_TILE), qt_last = (T - 1) / ATTB_TILE;
+  const AttWork wk = att_work(g.n_blk, false, g.BH, g.H, D, T, w);         // rows = keys here; first key blocks first: the longest walks
+  const int kb = wk.blk;
+  const int64_t C = wk.C, ld = wk.ld;
+  const float* qbase = g.qkv + (int64_t)wk.b * T * ld + (int64_t)wk.hd * D;
+  const float* gbase = g.dout + (int64_t)wk.b * T * C + (int64_t)wk.hd * D;
+  const float* lbase = g.lse + (int64_t)wk.bh * T;
+  const float* dbase = g.delta + (int64_t)wk.bh * T;
+  const int krow = wk.row0 + l31, kclamp = min(krow, T - 1);
+  const int qt_first = kb * (ATT_BLOCK / ATT_TILE), qt_last = (T - 1) / ATT_TILE;
 
   float k[HALF], v[HALF];
-  attb_load_half_row<D>(k, qbase + C + (int64_t)kclamp * ld + HALF * h, POW2 ? 1.0f / g.sqrt_d : 1.0f);
-  attb_load_half_row<D>(v, qbase + 2 * C + (int64_t)kclamp * ld + HALF * h, 1.0f);
+  att_load_half_row<D>(k, qbase + C + (int64_t)kclamp * ld + HALF * h, POW2 ? 1.0f / g.sqrt_d : 1.0f);
+  att_load_half_row<D>(v, qbase + 2 * C + (int64_t)kclamp * ld + HALF * h, 1.0f);
 
-  attb_f32x16 dk[NDB], dv[NDB];
-#pragma unroll
-  for (int i = 0; i < NDB; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { dk[i][e] = 0.f; dv[i][e] = 0.f; }
+  att_f32x16 dk[NDB], dv[NDB];
+  att_zero(dk);
+  att_zero(dv);
 
-  AttbRows<D> rq, rg;
-  AttbCols<D> cq, cg;
+  AttRows<D> rq, rg;
+  AttCols<D> cq, cg;
   float r_lse = 0.f, r_delta = 0.f;              // threads 0..31: one query's lse and delta (0 at positions >= T, never used)
   auto load_tile = [&](int q0) {
-    attb_load_rows<D>(rq, qbase, ld, q0, T, tid);
-    attb_load_rows<D>(rg, gbase, C, q0, T, tid);
-    attb_load_cols<D>(cq, qbase, ld, q0, T, tid);
-    attb_load_cols<D>(cg, gbase, C, q0, T, tid);
-    if (tid < ATTB_TILE) {
+    att_load_rows<D>(rq, qbase, ld, q0, T, tid);
+    att_load_rows<D>(rg, gbase, C, q0, T, tid);
+    att_load_cols<D>(cq, qbase, ld, q0, T, tid);
+    att_load_cols<D>(cg, gbase, C, q0, T, tid);
+    if (tid < ATT_TILE) {
       const bool in = q0 + tid < T;
       r_lse = in ? lbase[q0 + tid] : 0.f;
       r_delta = in ? dbase[q0 + tid] : 0.f;
     }
   };
-  load_tile(qt_first * ATTB_TILE);
+  load_tile(qt_first * ATT_TILE);
   for (int qt = qt_first; qt <= qt_last; ++qt) {
     __syncthreads();
-    attb_store_rows<D>(rq, Qs, tid);
-    attb_store_rows<D>(rg, Gs, tid);
-    attb_store_cols<D>(cq, Qt, tid);
-    attb_store_cols<D>(cg, Gt, tid);
-    if (tid < ATTB_TILE) { Ls[tid] = r_lse; Ds[tid] = r_delta; }
+    att_store_rows<D>(rq, Qs, tid);
+    att_store_rows<D>(rg, Gs, tid);
+    att_store_cols<D>(cq, Qt, tid);
+    att_store_cols<D>(cg, Gt, tid);
+    if (tid < ATT_TILE) { Ls[tid] = r_lse; Ds[tid] = r_delta; }
     __syncthreads();
-    if (qt < qt_last) load_tile((qt + 1) * ATTB_TILE);
-    if (!active || qt < my_diag) continue;       // query tiles before this wavefront's diagonal see none of its keys
+    if (qt < qt_last) load_tile((qt + 1) * ATT_TILE);
+    if (!wk.active || qt < wk.diag) continue;    // query tiles before this wavefront's diagonal see none of its keys
 
     // ---- S = Q . K^T and dP = dO . V^T: register e of lane half h = query 4h + (e & 3) + 8 (e >> 2), lane & 31 = key
-    attb_f32x16 s = attb_rows_times_regs<D>(Qs + l31 * KLD + HALF * h, k);
-    attb_f32x16 dp = attb_rows_times_regs<D>(Gs + l31 * KLD + HALF * h, v);
-    const bool diag = qt == my_diag;
-    const int q_left = T - qt * ATTB_TILE;       // queries of this tile at positions < T (>= 32 except in the last tile)
+    att_f32x16 s = att_rows_times_regs<D>(Qs + l31 * KLD + HALF * h, k);
+    att_f32x16 dp = att_rows_times_regs<D>(Gs + l31 * KLD + HALF * h, v);
+    const bool diag = qt == wk.diag;
+    const int q_left = T - qt * ATT_TILE;       // queries of this tile at positions < T (>= 32 except in the last tile)
 #pragma unroll
     for (int gi = 0; gi < 4; ++gi) {
       const float4 l4 = *reinterpret_cast<const float4*>(Ls + 8 * gi + 4 * h);
@@ -353,14 +212,14 @@ __global__ __launch_bounds__(256, 1) void causal_attention_bwd_dkv_kernel(AttBwd
       }
     }
     // ---- dV^T += dO^T . P and dK^T += Q^T . dS
-    attb_cols_times_cd<NDB>(dv, Gt + l31 * ATTB_TLD + 4 * h, s);
-    attb_cols_times_cd<NDB>(dk, Qt + l31 * ATTB_TLD + 4 * h, dp);
+    att_cols_times_cd<NDB>(dv, Gt + l31 * ATT_TLD + 4 * h, s);
+    att_cols_times_cd<NDB>(dk, Qt + l31 * ATT_TLD + 4 * h, dp);
   }
 
-  if (!active || krow >= T) return;
-  float* op = g.dqkv + ((int64_t)b * T + krow) * ld + (int64_t)hd * D;
-  attb_store_acc<D, NDB, POW2>(dk, op + C, h, 1.0f / g.sqrt_d, g.sqrt_d);
-  attb_store_acc<D, NDB, true>(dv, op + 2 * C, h, 1.0f, 1.0f);
+  if (!wk.active || krow >= T) return;
+  float* op = g.dqkv + ((int64_t)wk.b * T + krow) * ld + (int64_t)wk.hd * D;
+  att_store_acc<D, NDB, POW2>(dk, op + C, h, 1.0f / g.sqrt_d, g.sqrt_d);
+  att_store_acc<D, NDB, true>(dv, op + 2 * C, h, 1.0f, 1.0f);
 }
 
 template <int D>
@@ -376,21 +235,11 @@ static int launch_attention_bwd(const AttBwdArgs& g, hipStream_t st) {
   return check_launch("spq_causal_attention_bwd (dk, dv)");
 }
 
-// nullptr when the shape is served, else the reason
-static const char* attention_bwd_refusal(int64_t B, int64_t T, int64_t n_head, int64_t head_dim) {
-  if (!(head_dim == 16 || head_dim == 32 || head_dim == 64)) return "head_dim must be 64 (or 16, 32)";
-  if (B < 1 || T < 1 || n_head < 1) return "B, T and n_head must be at least 1";
-  const int64_t n_blk = (T + ATTB_BLOCK - 1) / ATTB_BLOCK;
-  if (T >= (1 << 24) || n_head >= (1 << 16) || B >= ((int64_t)1 << 31) || B * n_head * n_blk >= ((int64_t)1 << 31))
-    return "problem too large for one launch";
-  return nullptr;
-}
-
 }  // namespace spq
 
 extern "C" int64_t spq_causal_attention_bwd_workspace_bytes(int64_t B, int64_t T, int64_t n_head, int64_t head_dim) {
   using namespace spq;
-  if (const char* why = attention_bwd_refusal(B, T, n_head, head_dim)) {
+  if (const char* why = attention_refusal(B, T, n_head, head_dim, true)) {
     set_error("spq_causal_attention_bwd_workspace_bytes: %s (B=%lld T=%lld n_head=%lld head_dim=%lld)", why, (long long)B,
               (long long)T, (long long)n_head, (long long)head_dim);
     return SPQ_ERR_UNSUPPORTED;
@@ -404,7 +253,7 @@ extern "C" int spq_causal_attention_bwd(const float* qkv, const float* out, cons
   using namespace spq;
   SPQ_REQUIRE(qkv && out && lse && dout && dqkv && workspace, "spq_causal_attention_bwd: null pointer");
   // validate everything, then launch (DESIGN.md 3.3 "host side"): a refusal enqueues nothing
-  const char* why = attention_bwd_refusal(B, T, n_head, head_dim);
+  const char* why = attention_refusal(B, T, n_head, head_dim, true);
   if (!why && !(aligned16(qkv) && aligned16(out) && aligned16(lse) && aligned16(dout) && aligned16(dqkv) && aligned16(workspace)))
     why = "pointers must be 16-byte aligned";
   if (!why && workspace_bytes < (size_t)(B * n_head * T) * sizeof(float)) why = "workspace too small";
@@ -416,7 +265,7 @@ extern "C" int spq_causal_attention_bwd(const float* qkv, const float* out, cons
   AttBwdArgs g;
   g.qkv = qkv; g.out = out; g.lse = lse; g.dout = dout; g.dqkv = dqkv;
   g.delta = static_cast<const float*>(workspace); g.delta_out = static_cast<float*>(workspace);
-  g.T = (int)T; g.H = (int)n_head; g.BH = (int)(B * n_head); g.n_blk = (int)((T + ATTB_BLOCK - 1) / ATTB_BLOCK);
+  g.T = (int)T; g.H = (int)n_head; g.BH = (int)(B * n_head); g.n_blk = (int)((T + ATT_BLOCK - 1) / ATT_BLOCK);
   g.sqrt_d = (float)sqrt((double)head_dim);
   hipStream_t st = (hipStream_t)stream;
   switch (head_dim) {

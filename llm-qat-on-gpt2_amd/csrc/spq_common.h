@@ -11,6 +11,8 @@ namespace spq {
 // ---- host: thread-local error message ----------------------------------------------------------
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+// the causal attention core, forward or backward: nullptr when the shape is served, else the reason (spq_attention.hip)
+const char* attention_refusal(int64_t B, int64_t T, int64_t n_head, int64_t head_dim, bool backward);
 
 #define SPQ_REQUIRE(cond, ...)            \
   do {                                    \
