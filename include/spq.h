@@ -95,6 +95,8 @@ int spq_device_arch(char* buf, int buflen);
  * (per_channel=0, then min_io/max_io hold 1 value).  log_domain=0: running min/max of x.
  * log_domain=1: running min/max of log2(clamp(|x|, eps)), skipped when no element has |x| > eps, except
  * that a first batch without such an element fills both with log_eps_fill (= fp32 log2(eps), :194-197).
+ * NaN propagates as in torch: a NaN element makes both statistics of its channel NaN.  In the `|x| > eps` test a NaN
+ * compares false, but it hides no other element: the elements next to it still count.
  * first_batch!=0 assigns, otherwise merges (minimum/maximum) into min_io/max_io, in place.
  * workspace: spq_stats_workspace_bytes() bytes, 16-byte aligned.
  * ------------------------------------------------------------------------------------------------- */
@@ -131,10 +133,13 @@ int spq_fakequant_transposed(const float* x, int64_t rows, int64_t cols, const f
                              const float* zp, int per_channel, int bits, int qtype, int symmetric,
                              float out_scaling, float* out_f32, spq_stream_t stream);
 
-/* scale_out2 = {2^G, 2^-G} (device) with max|x| * 2^G in [2^13, 2^14): the x_limb_scale of SPQ_PATH_F16X3 for a tensor
- * that has no calibrated range -- the incoming gradient g of the backward contraction g . FQ(W)
- * (quantization_methods.py:25-28: the straight-through backward passes g unchanged).  One HBM pass over x, no host
- * synchronisation.  workspace: SPQ_LIMB_SCALE_WORKSPACE_BYTES bytes, 16-B aligned. */
+/* scale_out2 = {2^G, 2^-G} (device): the x_limb_scale of SPQ_PATH_F16X3 for a tensor that has no calibrated range -- the
+ * incoming gradient g of the backward contraction g . FQ(W) (quantization_methods.py:25-28: the straight-through backward
+ * passes g unchanged).  With m = max|x| and the fp32 product m * (1 + 2^-10) = f * 2^e, f in [0.5, 1):  G = 14 - e, clamped
+ * to [-100, 100].  So it is the GUARDED value m * (1 + 2^-10) * 2^G that lies in [2^13, 2^14); m * 2^G itself lies in
+ * [2^13 / (1 + 2^-10), 2^14 / (1 + 2^-10)): always below 2^14, and below 2^13 only for an m within 2^-10 (relative) under a
+ * power of two.  {1, 1} for an all-zero tensor and for one that holds an Inf; NaN elements are ignored.  One HBM pass over
+ * x, no host synchronisation.  workspace: SPQ_LIMB_SCALE_WORKSPACE_BYTES bytes, 16-B aligned. */
 #define SPQ_LIMB_SCALE_WORKSPACE_BYTES 16384
 int spq_dynamic_limb_scale(const float* x, int64_t n, float* scale_out2, void* workspace, size_t workspace_bytes,
                            spq_stream_t stream);

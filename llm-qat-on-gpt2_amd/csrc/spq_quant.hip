@@ -19,6 +19,10 @@ constexpr int kMaxSlabs = 256;
 // torch's min / max reductions propagate NaN (a diverged activation must surface as a NaN scale, not a plausible finite one);
 // v_min / v_max drop it.  The scan keeps a per-lane flag (one compare per element) and poisons its partial at the end; every
 // combine after that is NaN-propagating.
+// ABS (log domain) poisons the minimum only: the partial MAXIMUM stays the largest non-NaN magnitude, because the "any element
+// above eps" test (stats_any_kernel) is `(|x| > eps).any()`, where a NaN compares false but the elements next to it still
+// count -- a NaN partial maximum would hide its whole slab from that test.  stats_merge_kernel makes a channel's maximum NaN
+// wherever its minimum is.
 template <bool ABS>
 __device__ __forceinline__ void acc_minmax(float v, float& lo, float& hi, bool& nan) {
   if (ABS) v = fabsf(v);
@@ -26,8 +30,9 @@ __device__ __forceinline__ void acc_minmax(float v, float& lo, float& hi, bool& 
   lo = fminf(lo, v);
   hi = fmaxf(hi, v);
 }
+template <bool ABS>
 __device__ __forceinline__ void poison(bool nan, float& lo, float& hi) {
-  if (nan) { lo = __builtin_nanf(""); hi = lo; }
+  if (nan) { lo = __builtin_nanf(""); if (!ABS) hi = lo; }
 }
 
 template <bool ABS>
@@ -51,7 +56,7 @@ __global__ __launch_bounds__(kStatsBlock) void stats_rows_kernel(const float* __
   } else {
     for (int64_t i = lane; i < len; i += 64) acc_minmax<ABS>(p[i], lo, hi, nan);
   }
-  poison(nan, lo, hi);
+  poison<ABS>(nan, lo, hi);
   lo = wave_min_nan(lo);
   hi = wave_max_nan(hi);
   if (lane == 0) { pmin[row] = lo; pmax[row] = hi; }
@@ -96,7 +101,7 @@ __global__ __launch_bounds__(kStatsBlock) void stats_cols_kernel(const float* __
   }
   __shared__ float s_lo[4][64 * W], s_hi[4][64 * W];
 #pragma unroll
-  for (int j = 0; j < W; ++j) { poison(nanw[j], lo[j], hi[j]); s_lo[ty][tx * W + j] = lo[j]; s_hi[ty][tx * W + j] = hi[j]; }
+  for (int j = 0; j < W; ++j) { poison<ABS>(nanw[j], lo[j], hi[j]); s_lo[ty][tx * W + j] = lo[j]; s_hi[ty][tx * W + j] = hi[j]; }
   __syncthreads();
   if (ty == 0 && c0 < cols) {
 #pragma unroll
@@ -130,7 +135,7 @@ __global__ __launch_bounds__(kStatsBlock) void stats_flat_kernel(const float* __
   } else {
     for (int64_t i = b0 + threadIdx.x; i < b1; i += kStatsBlock) acc_minmax<ABS>(x[i], lo, hi, nan);
   }
-  poison(nan, lo, hi);
+  poison<ABS>(nan, lo, hi);
   lo = wave_min_nan(lo); hi = wave_max_nan(hi);
   __shared__ float s_lo[kStatsBlock / 64], s_hi[kStatsBlock / 64];
   if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; }
@@ -186,6 +191,7 @@ __global__ __launch_bounds__(256) void stats_merge_kernel(const float* __restric
   if (w != 0 || c >= chan) return;
   float lo = nan_min(nan_min(s_lo[0][cl], s_lo[1][cl]), nan_min(s_lo[2][cl], s_lo[3][cl]));
   float hi = nan_max(nan_max(s_hi[0][cl], s_hi[1][cl]), nan_max(s_hi[2][cl], s_hi[3][cl]));
+  if (log_domain && lo != lo) hi = lo;                                  // the scans poison only the minimum (see poison)
   if (!any) {
     if (first) { min_io[c] = log_eps_fill; max_io[c] = log_eps_fill; }  // :194-197
     return;                                                             // later batch: untouched
@@ -441,8 +447,9 @@ __global__ __launch_bounds__(1024) void ln_bwd_merge_kernel(const float* __restr
   if (dbias) dbias[c] = sb;
 }
 
-// {2^G, 2^-G} with max|x| * 2^G in [2^13, 2^14): the scale of the two-fp16-limb operand of an un-quantised tensor
-// (the incoming gradient of the backward GEMM).  One block over the per-slab maxima of stats_flat_kernel<true>.
+// {2^G, 2^-G} with max|x| * (1 + 2^-10) * 2^G in [2^13, 2^14) (see include/spq.h): the scale of the two-fp16-limb operand of
+// an un-quantised tensor (the incoming gradient of the backward GEMM).  One block over the per-slab maxima of
+// stats_flat_kernel<true>, which are the largest non-NaN magnitudes.
 __global__ __launch_bounds__(256) void limb_scale_kernel(const float* __restrict__ pmax, int S, float* __restrict__ out2) {
   float m = 0.f;
   for (int i = threadIdx.x; i < S; i += 256) m = fmaxf(m, pmax[i]);
