@@ -229,6 +229,46 @@ int spq_causal_attention_bwd(const float* qkv, const float* out, const float* ls
                              spq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The language-model loss of SPLMHeadModel.forward (models_sp.py:443-449), fp32:
+ *     shift_logits = logits[..., :-1, :];  loss = F.cross_entropy(shift_logits.view(-1, V), labels[..., 1:].view(-1))
+ * read from the logits where they lie: no shifted copy, no log_softmax tensor, no gradient of a slice.
+ * logits: [B, T, V] contiguous.  labels: [B, T] int64.  shift = 1: row (b, t), t < T - 1, is scored against labels[b, t + 1] and
+ *   row T - 1 has no label; shift = 0: row (b, t) against labels[b, t] (a [rows, V] problem is B = 1, T = rows).
+ * A row COUNTS when it has a label and that label is not ignore_index.
+ *
+ * spq_lm_cross_entropy_fwd, two launches:
+ *   lse   [2, B, T]  lse[0] = log sum_v exp(x_v) of every row, counted or not (one pass, online maximum and sum);
+ *                    lse[1] = the rounding residual of lse[0], the rounding error of the addition max + log(sum) that made lse[0].
+ *                    (Near logits of 1e4 one fp32 holds it to 5e-4 only -- fifty times the project's bar on the probabilities
+ *                    the backward forms from it.)
+ *   nll   [B, T]     lse - x_label of a counted row, formed as (max - x_label) + log(sum); 0 for a row that does not count;
+ *                    NaN for a label outside [0, V) that is not ignore_index (the logits are never read out of range).
+ *   loss  [2]        loss[0] = the sum of nll over the counted rows, loss[1] = loss[0] / count (NaN when count = 0, as torch
+ *                    gives).  Summed in double by one workgroup in an order that depends on B * T alone: no atomics.
+ *   count [1]        the number of counted rows (int64).  A row with an out-of-range label counts; sum and mean are then NaN.
+ * spq_lm_cross_entropy_bwd, one launch:
+ *   dlogits [B, T, V]  g * (exp(x_v - lse) - [v == label]) on a counted row, exact zeros on every other row (row T - 1 under the
+ *                    shift included): every element is written.  NaN on a row whose label is out of range.
+ *   g is grad[0] / count[0] (mean), grad[0] with count = NULL (sum), or grad_per_row[b * (T - shift) + t] (none; grad = NULL):
+ *   all read on the device.  Exactly one of grad / grad_per_row is given.
+ * Domain: B, T, V >= 1 with B * T and V below 2^31 (T = 1 under the shift is served: no row counts).  logits and dlogits need
+ * 4-byte alignment only -- V = 50257 is odd, so rows start at all four phases of a 16-byte line anyway -- labels and count 8-byte,
+ * everything else 4-byte.  A row is cut into 16-byte pieces counted from ITS first element, so its bits do not depend on the phase.
+ * -inf logits are allowed next to a finite one (probability 0, gradient 0).  A null pointer returns SPQ_ERR_INVALID; a size below
+ * 1, a problem too large, a shift other than 0 / 1 or a misaligned pointer SPQ_ERR_UNSUPPORTED; both before anything is enqueued,
+ * and spq_last_error names the function and the argument.  No workspace, no allocation, no host synchronisation; capturable.
+ * Deterministic, and row (b, t) -- its nll, lse and gradient under a fixed g -- is a function of that row and its label alone: it
+ * does not change with B, T or the other rows (a NaN logit stays in its row).
+ * ------------------------------------------------------------------------------------------------- */
+int spq_lm_cross_entropy_fwd(const float* logits, const int64_t* labels, int64_t B, int64_t T, int64_t V, int shift,
+                             int64_t ignore_index, float* nll, float* lse, float* loss /* [2]: sum, mean */, int64_t* count,
+                             spq_stream_t stream);
+int spq_lm_cross_entropy_bwd(const float* logits, const int64_t* labels, const float* lse, int64_t B, int64_t T, int64_t V,
+                             int shift, int64_t ignore_index, const float* grad /* [1], or NULL */,
+                             const float* grad_per_row /* [B, T - shift], or NULL */, const int64_t* count /* NULL: no division */,
+                             float* dlogits, spq_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * The path's only exchange step: before finish_calibration every rank merges the running
  * statistics of its input quantizers (quantization.py:202-207 across ranks) with ONE in-place
  * all-reduce(MAX) over the flat fp32 buffer [-min_0 .. | max_0 ..] -- ncclAllReduce(ncclFloat, ncclMax) of

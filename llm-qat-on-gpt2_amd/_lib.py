@@ -77,6 +77,8 @@ SIGNATURES = {
     "spq_causal_attention_fwd": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p]),
     "spq_causal_attention_bwd_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "spq_causal_attention_bwd": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _sz, _p]),
+    "spq_lm_cross_entropy_fwd": (_int, [_p, _p, _i64, _i64, _i64, _int, _i64, _p, _p, _p, _p, _p]),
+    "spq_lm_cross_entropy_bwd": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _i64, _p, _p, _p, _p, _p]),
     "spq_debug_reload_switches": (_int, []),
     "spq_debug_split_k": (_int, [_i64, _i64, _i64, _i64, _int]),
     "spq_version": (_int, []),

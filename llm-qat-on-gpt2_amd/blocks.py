@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from . import _lib, attention
+from . import _lib, attention, lm_loss
 from .sp_linear import SPLinearWithLoRA
 
 
@@ -369,6 +369,8 @@ class SPLMHeadModel(nn.Module):
     """models_sp.py:390-458: ``transformer`` (SPModel) + the tied, un-quantized ``lm_head`` -- the object the reference's
     checkpoints describe (state-dict keys ``transformer.*`` + ``lm_head.weight``, deploy.py:143, main_sp_eval.py:70)."""
 
+    use_hip_loss = False        # set_lm_loss(model, 'hip'): the loss on spq_lm_cross_entropy_fwd / _bwd where they apply
+
     def __init__(self, config):
         super().__init__()
         self.config = config
@@ -395,10 +397,30 @@ class SPLMHeadModel(nn.Module):
         hidden_states, all_hidden_states = out if output_hidden_states else (out, None)
         logits = self.lm_head(hidden_states)
         loss = None
-        if labels is not None:
+        if labels is not None and self.use_hip_loss and lm_loss.served(logits, labels):
+            # the same loss from the logits where they lie: no shifted copy, no log_softmax tensor
+            loss = lm_loss.lm_cross_entropy(logits, labels)
+        elif labels is not None:
             shift_logits = logits[..., :-1, :].contiguous()
             shift_labels = labels[..., 1:].contiguous()
             loss = nn.functional.cross_entropy(shift_logits.view(-1, shift_logits.size(-1)), shift_labels.view(-1))
         if return_dict or output_hidden_states:
             return {'loss': loss, 'logits': logits, 'hidden_states': all_hidden_states}
         return {'loss': loss, 'logits': logits} if loss is not None else logits
+
+
+LM_LOSSES = ('hip', 'torch')
+
+
+def set_lm_loss(model: nn.Module, loss: str) -> int:
+    """Choose the loss of every ``SPLMHeadModel`` in ``model``: 'hip' (``lm_loss.lm_cross_entropy`` where it applies -- fp32 logits
+    and int64 labels on a GPU -- and torch's elsewhere) or 'torch' (the default: the reference's two lines).  Returns the number of
+    modules set."""
+    if loss not in LM_LOSSES:
+        raise ValueError(f"lm loss must be one of {LM_LOSSES}, got {loss!r}")
+    n = 0
+    for m in model.modules():
+        if isinstance(m, SPLMHeadModel):
+            m.use_hip_loss = loss == 'hip'
+            n += 1
+    return n
